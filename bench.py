@@ -12,10 +12,18 @@ scaling: every rank encodes its own 10M rows), no data-path collective; the
 timed region is bracketed by barrier + synchronize and the max over ranks is
 taken.
 
-Extra fields: ``roofline`` for the dominant kernel (per-launch time from HIP
-events on the launch stream inside the timed region), ``kernels`` (per-level
-breakdown), ``cpu_baseline`` (the oracle's CPU encode timed on this host on a
-bounded sample, rank 0, N=1 only).
+A plain run does what the headline figure needs and no more: set up (codebooks,
+rows), warm up, time ``--steps`` steps, write the last step's output when
+``--dump-outputs DIR`` is given, print the result line.  Its extra fields come
+from HIP events recorded inside the timed region: ``roofline`` for the dominant
+kernel and ``kernels`` (per-level breakdown).
+
+``--full`` adds everything that takes runs of its own, after the timed region:
+``kernels.*.rescored_rows`` (one counting encode before it), ``train``,
+``train_balanced``, ``parity`` (the timed output against the exact oracle),
+``cpu_baseline`` / ``cpu_baselines_8d`` (the oracle's CPU encode timed on this
+host on a bounded sample, rank 0, N=1 only), ``config0`` and, at N > 1,
+``gather_ids_ms``.
 """
 from __future__ import annotations
 
@@ -44,6 +52,7 @@ BF16_PEAK_TFLOPS = 2500.0      # dense bf16 MFMA spec
 D = 512
 NEED = [128, 128, 256]
 N_CAND = 2560
+DUMP_MAX_ROWS = 2_000_000      # --dump-outputs: 2M rows x (3 float32 IDs + a float64 row number) = 40 MB
 
 
 def parse():
@@ -75,6 +84,14 @@ def parse():
                          "its CPU restatement on a bounded sample (field 'config0')")
     ap.add_argument("--parity-rows", type=int, default=2048,
                     help="rows of the timed output checked against the exact CPU oracle after the run (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements (rescored-row counts, train, train_balanced, parity, CPU "
+                         "baselines, config0, gather_ids at N > 1); without it --cpu-sample, --no-cpu, "
+                         "--balanced-rows, --train-iters, --side-budget, --config0 and --parity-rows have no effect")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's output (the int32 IDs encode_shard returned) "
+                         "as DIR/ids.npy (float32 [m, levels]) and DIR/ids_rows.npy (float64 [m], the rows they "
+                         "belong to): all rows, or a fixed seeded sample of DUMP_MAX_ROWS of them")
     a = ap.parse_args()
     global NEED, N_CAND, PRESET
     PRESET = a.preset
@@ -520,6 +537,23 @@ def check_sample(x, out, cb, rows):
     return {"rows_checked": rows, "mismatches": bad, "against": "oracle/rq_oracle.py encode(exact=True), evenly spaced rows"}
 
 
+def dump_outputs(path, out, rank, world):
+    """--dump-outputs: the timed path's last output (int32 IDs [n, levels] on the device) as float32, with the
+    rows' numbers as float64; beyond DUMP_MAX_ROWS rows a sorted sample drawn with a fixed seed, the same rows
+    in every run of the same arguments.  One pair of files per rank (suffix _rank<r> when N > 1)."""
+    d = Path(path)
+    d.mkdir(parents=True, exist_ok=True)
+    n = out.shape[0]
+    if n > DUMP_MAX_ROWS:
+        rows = np.sort(np.random.default_rng(20240).choice(n, DUMP_MAX_ROWS, replace=False))
+        ids = out[torch.from_numpy(rows).to(out.device)]
+    else:
+        rows, ids = np.arange(n), out
+    suffix = f"_rank{rank}" if world > 1 else ""
+    np.save(d / f"ids{suffix}.npy", ids.cpu().numpy().astype(np.float32))
+    np.save(d / f"ids_rows{suffix}.npy", rows.astype(np.float64))
+
+
 def main():
     args = parse()
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -570,8 +604,9 @@ def main():
         enc.encode(x)
     torch.cuda.synchronize()
     rescored = []
-    enc.encode(x, count_rescored=True)
-    rescored = list(enc.last_rescored)
+    if args.full:  # a run of its own: the rows each level re-scores (kernels.*.rescored_rows)
+        enc.encode(x, count_rescored=True)
+        rescored = list(enc.last_rescored)
 
     encmod.ops.assign = assign_hook
     encmod.ops.residual = timer.wrap("residual", orig_res)
@@ -589,8 +624,10 @@ def main():
         tdist.barrier()
     elapsed = time.perf_counter() - t0
     encmod.ops.assign, encmod.ops.residual, encmod.ops.bucket = orig_assign, orig_res, orig_bucket
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, rank, world)
     gather_ms = None
-    if dist:  # outside the timed region: the int32 IDs of every rank to every rank (the jsonl writer's input)
+    if dist and args.full:  # outside the timed region: the int32 IDs of every rank to every rank (the jsonl writer's input)
         try:
             t_g = time.perf_counter()
             ids_all = model.gather_ids(out)
@@ -677,9 +714,15 @@ def main():
     }
     if gather_ms is not None:
         line["gather_ids_ms"] = round(gather_ms, 3) if isinstance(gather_ms, float) else {"error": gather_ms}
+    if not args.full:  # a plain run ends here: the headline line alone
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if dist:
+            tdist.destroy_process_group()
+        return
     # The encode line is complete here.  The side measurements below run collectives at N > 1; a hang
     # there must not cost the line (SideWatchdog).
-    dog = SideWatchdog(line, args.side_budget or (600.0 if world == 1 else 300.0), rank).start()
+    dog =SideWatchdog(line, args.side_budget or (600.0 if world == 1 else 300.0), rank).start()
     if args.train_iters > 0:
         try:
             t_ms, rps = train_iterations(x, torch.from_numpy(cb["c0"]).to(dev).float(), args.train_iters, world,

@@ -112,7 +112,10 @@ def g_residual():
     rs = s._get_residuals(torch.from_numpy(X), km).numpy()
     out["res_plain_head"] = rs[:256]
     out["res_plain_sha"] = np.array(synth.sha256(rs))
-    save("residual", ids=ids.numpy().astype(np.int64), **out)
+    # two files: together the three 256-row heads would pass the 1 MiB limit on a committed file
+    split = {k: v for k, v in out.items() if k.startswith("res_g128_384_")}
+    save("residual", ids=ids.numpy().astype(np.int64), **{k: v for k, v in out.items() if k not in split})
+    save("residual_g128_384", **split)
 
 
 # --- G4: Lloyd update incl. an empty cluster (fit, balanced=False, 1 iteration)

@@ -45,6 +45,41 @@ def test_side_watchdog_prints_the_encode_line_and_exits_nonzero(capsys):
     assert capsys.readouterr().out == ""
 
 
+def test_plain_run_is_the_default_and_full_is_an_option(monkeypatch):
+    import sys
+    sys.path.insert(0, str(REPO))
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "3"])
+    a = bench.parse()
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 3)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "d"
+
+
+def test_dump_outputs_writes_float_arrays_and_a_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs: every row of a small output; of a larger one the same sorted sample in every run,
+    float32 IDs beside their float64 row numbers."""
+    import sys
+    import numpy as np
+    import torch
+    sys.path.insert(0, str(REPO))
+    import bench
+    out = (torch.arange(3000, dtype=torch.int32).reshape(1000, 3) * 7) % 256
+    bench.dump_outputs(tmp_path / "all", out, rank=0, world=1)
+    ids, rows = np.load(tmp_path / "all" / "ids.npy"), np.load(tmp_path / "all" / "ids_rows.npy")
+    assert ids.dtype == np.float32 and rows.dtype == np.float64
+    assert np.array_equal(ids, out.numpy()) and np.array_equal(rows, np.arange(1000))
+    monkeypatch.setattr(bench, "DUMP_MAX_ROWS", 100)
+    for d in ("a", "b"):
+        bench.dump_outputs(tmp_path / d, out, rank=1, world=2)
+    ids, rows = np.load(tmp_path / "a" / "ids_rank1.npy"), np.load(tmp_path / "a" / "ids_rows_rank1.npy")
+    assert ids.shape == (100, 3) and len(np.unique(rows)) == 100 and (np.diff(rows) > 0).all()
+    assert np.array_equal(ids, out.numpy()[rows.astype(np.int64)])
+    assert np.array_equal(rows, np.load(tmp_path / "b" / "ids_rows_rank1.npy"))
+    assert np.array_equal(ids, np.load(tmp_path / "b" / "ids_rank1.npy"))
+
+
 def test_side_watchdog_quiet_when_done_in_time(capsys):
     import sys
     sys.path.insert(0, str(REPO))

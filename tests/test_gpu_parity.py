@@ -150,7 +150,7 @@ def test_residual(gd, norm):
 
 
 def test_residual_golden(golden):
-    g = golden("residual")
+    g = {**golden("residual"), **golden("residual_g128_384")}
     x, c = _data.residual_inputs()
     for tag, gd in (("g512", [512]), ("g128_384", [128, 384])):
         got = ops.residual(gpu(x), gpu(c), gpu(g["ids"].astype(np.int32)), gd, True).cpu().numpy()

@@ -39,7 +39,7 @@ def test_assign_ties_take_lowest_index(golden):
 @pytest.mark.parametrize("tag,gd,norm", [("g512", [512], True), ("g128_384", [128, 384], True),
                                          ("plain", [512], False)])
 def test_residual_matches_reference(golden, tag, gd, norm):
-    g = golden("residual")
+    g = {**golden("residual"), **golden("residual_g128_384")}
     x, c = _data.residual_inputs()
     r = O.residual(x, c, g["ids"], gd, normalize=norm)
     ref = g[f"res_{tag}_head"]

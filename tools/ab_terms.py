@@ -20,5 +20,5 @@ def _forced(*a, **k):
 
 ops.assign = _forced
 if __name__ == "__main__":
-    sys.argv = ["bench.py", "--no-cpu", *sys.argv[1:]]
+    sys.argv = ["bench.py", "--full", "--no-cpu", *sys.argv[1:]]
     bench.main()

@@ -6,6 +6,7 @@ export TMPDIR=/tmp
 OUT=$GRAFT_REPO_ROOT/gpurun_out/${TAG:-ab}
 mkdir -p "$OUT"
 ARGS="--steps ${STEPS:-10} --warmup 2 --no-cpu --balanced-rows 0 --train-iters 0 --parity-rows ${PARITY:-0} --config0 0 ${BENCH_ARGS:-}"
+[ "${PARITY:-0}" != 0 ] && ARGS="--full $ARGS"  # the parity sample is a side measurement
 for spec in $AB; do
   name=${spec%%:*}; envs=${spec#*:}
   env_args=""; [ "$envs" != "-" ] && env_args=$(echo "$envs" | tr ',' ' ')

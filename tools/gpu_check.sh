@@ -11,6 +11,7 @@ timeout -k 10 ${TEST_T:-900} python -m pytest tests -m gpu -q -rA ${PYTEST_ARGS:
 rc=$?; echo "pytest rc=$rc"; tail -30 "$OUT/gpu_tests.log"
 if fatal $rc; then exit $rc; fi
 [ "${SKIP_BENCH:-0}" = 1 ] && exit $rc
+BENCH_ARGS="--full ${BENCH_ARGS:-}"  # the side measurements too (parity, training, CPU baselines)
 timeout -k 10 ${BENCH_T:-600} python bench.py ${BENCH_ARGS:-} > "$OUT/bench.log" 2>&1
 rc2=$?; echo "bench rc=$rc2"; tail -5 "$OUT/bench.log"
 if [ $rc2 -ne 0 ]; then exit $rc2; fi
