@@ -103,11 +103,12 @@ __global__ void centers_scale_kernel(float* __restrict__ scale) {
 
 constexpr int kSplitDim = 512;  // widest row of the candidate-split form
 // CW candidate groups (CW > 1: the candidate-split form, 4 CW waves, see assign_screen_kernel)
-template <int NT, int S, bool T3, int CW = 1>
+template <int NT, int S, bool T3, int CW = 1, int XF = RQSID_X_F32>
 struct ScreenLayout {
+  static constexpr int kXS = x_stage_bytes(XF);             // row image of a stage (follows the row format)
   static constexpr int kCHalf = CW * NT * 32 * 64;         // CW*NT*32 candidates x 32 fp16 dims
   static constexpr int kCStage = kCHalf * (T3 ? 2 : 1);     // hi (+ lo) centre images
-  static constexpr int kStage = kXStage + kCStage;
+  static constexpr int kStage = kXS + kCStage;
   static constexpr int kMeta = S * kStage;       // float4 {|c|^2, |c|, e0, 0} per candidate of the pass
   // CW > 1 (single pass only): meta is the SoA |c|^2, |c| plus the per-wave maxima, and rows are at
   // most kSplitDim wide, so a 3-stage ring of 48-KiB stages fits the 160 KiB of LDS
@@ -226,11 +227,20 @@ __device__ unsigned long long g_stamps_tile[8];
 // in ONE pass: the tile's rows stream from HBM once instead of once per 256 / 128-candidate pass.  The
 // waves of a row group share the row image (each issues 4/CW of its DMAs) and exchange their least
 // upper bounds and pass lists through LDS (pass_decide_cw).
-template <int NT, int S, int RL, bool NORM, bool T3, bool ONE, int CW = 1>
-__global__ __launch_bounds__(256 * CW, CW > 1 ? 2 : (T3 ? 2 : (S == 2 ? (NT == 4 ? 3 : 2) : ((NT == 4 && S <= 3) ? 2 : 1)))) void assign_screen_kernel(AssignParams p) {
+//
+// XF: the row format (RQSID_X_*).  The body is shared: assign_screen_kernel is its fp32-row build and
+// assign_screen_x16_kernel its 16-bit-row builds (fp16 / bf16 rows, CW = 1 only), which differ in the row
+// image alone (ScreenLayout::kXS, the DMA op count in P, the LDS read) and widen each row element to fp32
+// right after the LDS read (widen2), so row_frag and everything after it run the fp32 build's operation
+// sequence on the same values: the bound argument is unchanged.
+template <int NT, int S, int RL, bool NORM, bool T3, bool ONE, int CW, int XF>
+__device__ __forceinline__ void screen_tile(const AssignParams& p) {
   static_assert(CW == 1 || (ONE && (CW == 2 || CW == 4)), "candidate-split form: single-pass segments");
-  using L = ScreenLayout<NT, S, T3, CW>;
-  constexpr int kXOps = 4 / CW;  // x-row DMA ops per wave per chunk (a row group's 4 split over its CW waves)
+  static_assert(XF == RQSID_X_F32 || CW == 1, "16-bit rows: per-tile form only");
+  using L = ScreenLayout<NT, S, T3, CW, XF>;
+  constexpr bool X16 = XF != RQSID_X_F32;
+  constexpr int kXW = x_wave_bytes(XF);       // a wave's row image per stage
+  constexpr int kXOps = x_wave_ops(XF) / CW;  // x-row DMA ops per wave per chunk (a row group's split over its CW waves)
   constexpr int P = kXOps + (NT / 2) * (T3 ? 2 : 1);  // DMA ops per wave per chunk (centres: NT/2 per table)
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   // FP16 (and FP64) denormals flushed: a row value below the fp16 normal range converts to 0 (its
@@ -284,14 +294,23 @@ __global__ __launch_bounds__(256 * CW, CW > 1 ? 2 : (T3 ? 2 : (S == 2 ? (NT == 4
 
   // DMA sources for this wave's x rows: instruction i covers rows 8i + lane/8, 16-B slot lane%8 of the
   // LDS image holding global slot (lane%8) ^ swz(row)  (swz(row) = (row>>1)&7: conflict-free reads);
-  // CW > 1: the row group's instructions cg*kXOps .. +kXOps-1
-  const float* xsrc[kXOps];
+  // CW > 1: the row group's instructions cg*kXOps .. +kXOps-1.
+  // 16-bit rows: instruction i covers rows 16i + lane/4, slot lane%4 holding global slot (lane%4) ^
+  // ((row>>2)&3) (the centre hi image's layout)
+  const float* xsrc[kXOps];  // X16: 16-bit elements behind a float pointer (byte arithmetic below)
 #pragma unroll
   for (int i = 0; i < kXOps; ++i) {
-    const int rr = 8 * (cg * kXOps + i) + (lane >> 3);
-    const int grow = __shfl(my_row, rr);
-    const int slot = (lane & 7) ^ ((rr >> 1) & 7);
-    xsrc[i] = p.x + (int64_t)grow * dim + slot * 4;
+    if constexpr (X16) {
+      const int rr = 16 * i + (lane >> 2);
+      const int grow = __shfl(my_row, rr);
+      const int slot = (lane & 3) ^ ((rr >> 2) & 3);
+      xsrc[i] = reinterpret_cast<const float*>(reinterpret_cast<const uint16_t*>(p.x) + (int64_t)grow * dim + slot * 8);
+    } else {
+      const int rr = 8 * (cg * kXOps + i) + (lane >> 3);
+      const int grow = __shfl(my_row, rr);
+      const int slot = (lane & 7) ^ ((rr >> 1) & 7);
+      xsrc[i] = p.x + (int64_t)grow * dim + slot * 4;
+    }
   }
   // residual rows of this segment -> LDS (staged below, after the ring's first DMAs are in flight)
   float* lds_ca = reinterpret_cast<float*>(smem + L::kRes);
@@ -326,7 +345,7 @@ __global__ __launch_bounds__(256 * CW, CW > 1 ? 2 : (T3 ? 2 : (S == 2 ? (NT == 4
   float vn = 0.f, en = 0.f, en2 = 0.f, inv_den = 1.f, dr = 0.f;
   float4* lds_meta = reinterpret_cast<float4*>(smem + L::kMeta);
   const f32x16 zero16 = {};
-  const int xsw = (r >> 1) & 7;  // swizzle of this lane's row in the x image
+  const int xsw = X16 ? (r >> 2) & 3 : (r >> 1) & 7;  // swizzle of this lane's row in the x image
   const int csw = (r >> 2) & 3;  // swizzle of this lane's candidate row in the centre image
 
   const int npass = ONE ? 1 : (cnt + NT * 32 - 1) / (NT * 32);
@@ -355,13 +374,13 @@ __global__ __launch_bounds__(256 * CW, CW > 1 ? 2 : (T3 ? 2 : (S == 2 ? (NT == 4
     auto issue_op = [&](int c, int i, bool relaxed) {
       const uint32_t sb = lds0 + (uint32_t)((c % S) * L::kStage);
       if (i < kXOps) {
-        const void* src = xsrc[i] + c * kChunk;
-        const uint32_t dst = __builtin_amdgcn_readfirstlane(sb + rg * kXWaveBytes + (cg * kXOps + i) * 1024);
+        const void* src = xsrc[i] + c * (x_row_bytes(XF) / 4);
+        const uint32_t dst = __builtin_amdgcn_readfirstlane(sb + rg * kXW + (cg * kXOps + i) * 1024);
         if (relaxed) dma16_nt_r(src, dst); else dma16_nt(src, dst);
       } else {
         const int j = i - kXOps;
         const void* src = csrc[j] + c * kCStride;
-        const uint32_t dst = __builtin_amdgcn_readfirstlane(sb + kXStage + (wave * kCOps + j) * 1024);
+        const uint32_t dst = __builtin_amdgcn_readfirstlane(sb + L::kXS + (wave * kCOps + j) * 1024);
         if (relaxed) dma16_r(src, dst); else dma16(src, dst);
       }
     };
@@ -428,15 +447,24 @@ __global__ __launch_bounds__(256 * CW, CW > 1 ? 2 : (T3 ? 2 : (S == 2 ? (NT == 4
       return;
 #endif
       constexpr int NG = 2 * NT;
-      const unsigned char* xb = smem + (c % S) * L::kStage + rg * kXWaveBytes + r * 128;
+      const unsigned char* xb = smem + (c % S) * L::kStage + rg * kXW + r * x_row_bytes(XF);
       // centre image row of candidate t*32 + r: 64 B (1 term) or 128 B (T3: hi slots 0-3, lo 4-7)
-      const unsigned char* cbp = smem + (c % S) * L::kStage + kXStage + (cg * NT * 32 + r) * (T3 ? 128 : 64);
+      const unsigned char* cbp = smem + (c % S) * L::kStage + L::kXS + (cg * NT * 32 + r) * (T3 ? 128 : 64);
       const int tsw = (r >> 1) & 7;  // T3 image swizzle (the x image's)
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
-        const int q0 = 4 * ks + 2 * h;
-        const float4 xa = *reinterpret_cast<const float4*>(xb + ((q0 ^ xsw) << 4));
-        const float4 xc = *reinterpret_cast<const float4*>(xb + (((q0 + 1) ^ xsw) << 4));
+        float4 xa, xc;
+        if constexpr (X16) {  // the lane's 8 dims are one 16-B slot: widened here, fp32 from here on
+          const uint4 xw = *reinterpret_cast<const uint4*>(xb + (((2 * ks + h) ^ xsw) << 4));
+          widen2<XF, false>(xw.x, xa.x, xa.y);
+          widen2<XF, false>(xw.y, xa.z, xa.w);
+          widen2<XF, false>(xw.z, xc.x, xc.y);
+          widen2<XF, false>(xw.w, xc.z, xc.w);
+        } else {
+          const int q0 = 4 * ks + 2 * h;
+          xa = *reinterpret_cast<const float4*>(xb + ((q0 ^ xsw) << 4));
+          xc = *reinterpret_cast<const float4*>(xb + (((q0 + 1) ^ xsw) << 4));
+        }
         const int d0 = c * kChunk + 16 * ks + 8 * h;
         f16x8 bf, bl = {};
         if (pass == 0) row_frag<RL, NORM, T3, true>(xa, xc, lds_ca, lds_cb, d0, inv1, bf, bl, rs);
@@ -746,6 +774,19 @@ __global__ __launch_bounds__(256 * CW, CW > 1 ? 2 : (T3 ? 2 : (S == 2 ? (NT == 4
   push_work(p, h == 0 && row_valid && !definitive, lane, w);
 }
 
+constexpr int screen_min_blocks(int NT, int S, bool T3, int CW) {
+  return CW > 1 ? 2 : (T3 ? 2 : (S == 2 ? (NT == 4 ? 3 : 2) : ((NT == 4 && S <= 3) ? 2 : 1)));
+}
+template <int NT, int S, int RL, bool NORM, bool T3, bool ONE, int CW = 1>
+__global__ __launch_bounds__(256 * CW, screen_min_blocks(NT, S, T3, CW)) void assign_screen_kernel(AssignParams p) {
+  screen_tile<NT, S, RL, NORM, T3, ONE, CW, RQSID_X_F32>(p);
+}
+// 16-bit rows (XF = RQSID_X_F16 / RQSID_X_BF16): rqsid_assign_x
+template <int XF, int NT, int S, int RL, bool NORM, bool T3, bool ONE>
+__global__ __launch_bounds__(256, screen_min_blocks(NT, S, T3, 1)) void assign_screen_x16_kernel(AssignParams p) {
+  screen_tile<NT, S, RL, NORM, T3, ONE, 1, XF>(p);
+}
+
 // ---------------------------------------------------------------------------
 // exact re-score
 // ---------------------------------------------------------------------------
@@ -757,8 +798,8 @@ __global__ __launch_bounds__(256 * CW, CW > 1 ? 2 : (T3 ? 2 : (S == 2 ? (NT == 4
 constexpr int kRescoreMaxV = kMaxDim / 256;  // float4 per lane
 constexpr int kBatch = 8;
 
-template <int RL, bool NORM>
-__global__ __launch_bounds__(256) void assign_rescore_kernel(AssignParams p) {
+template <int RL, bool NORM, int XF>
+__device__ __forceinline__ void rescore_rows(const AssignParams& p) {
   const int lane = threadIdx.x & 63;
   const int wid = blockIdx.x * 4 + (threadIdx.x >> 6);
   const int nw = gridDim.x * 4;
@@ -769,7 +810,6 @@ __global__ __launch_bounds__(256) void assign_rescore_kernel(AssignParams p) {
   // segments (duplicated centres), and striding spreads them evenly over the waves.
   for (int64_t it = wid; it < nitems; it += nw) {
     const WorkItem w = p.work[p.work_idx ? p.work_idx[it] : it];
-    const float* xr = p.x + (int64_t)w.row * p.dim;
     const float* car = RL >= 1 ? p.ca + (int64_t)seg_row(p.seg_ca, w.seg) * p.dim : nullptr;
     const float* cbr = RL >= 2 ? p.cb + (int64_t)seg_row(p.seg_cb, w.seg) * p.dim : nullptr;
     const bool screened = w.n >= 1 || w.n == -1;  // the screen wrote den_out for these rows
@@ -779,7 +819,7 @@ __global__ __launch_bounds__(256) void assign_rescore_kernel(AssignParams p) {
     for (int m = 0; m < kRescoreMaxV; ++m) {
       const int i = lane + 64 * m;
       if (i < nv) {
-        float4 a = reinterpret_cast<const float4*>(xr)[i];
+        float4 a = load_row4<XF>(p.x, w.row, p.dim, i);
         if (RL >= 1) {
           const float4 c = reinterpret_cast<const float4*>(car)[i];
           a = make_float4(a.x - c.x, a.y - c.y, a.z - c.z, a.w - c.w);
@@ -895,6 +935,16 @@ __global__ __launch_bounds__(256) void assign_rescore_kernel(AssignParams p) {
     }
   }
 }
+// (the re-score kernels, like the screen: one body, an fp32-row build under the name the profiles key on and
+// 16-bit-row builds that widen the row as they load it, load_row4)
+template <int RL, bool NORM>
+__global__ __launch_bounds__(256) void assign_rescore_kernel(AssignParams p) {
+  rescore_rows<RL, NORM, RQSID_X_F32>(p);
+}
+template <int XF, int RL, bool NORM>
+__global__ __launch_bounds__(256) void assign_rescore_x16_kernel(AssignParams p) {
+  rescore_rows<RL, NORM, XF>(p);
+}
 
 // Two listed rows per wave (rows of at most kHalfDim dims): lanes 32 hh .. 32 hh + 31 re-score item
 // 2 wid + hh of the pass with 4 float4 of the row per lane; the same arithmetic, candidate batches and
@@ -919,9 +969,8 @@ constexpr int kOvfSlot = 56;  // workspace header int: overflow item count
 // checked against its slot's capacity; a write that would fall outside is dropped and its bit raised, so
 // a wrong count can only produce a reported error, never a store outside the workspace.
 // (kErrSlot and its bits: assign_common.h)
-template <int RL, bool NORM>
-__global__ __launch_bounds__(256) void assign_rescore_half_kernel(AssignParams p, const int32_t* __restrict__ ovf_list,
-                                                                  int mode) {
+template <int RL, bool NORM, int XF>
+__device__ __forceinline__ void rescore_half_rows(const AssignParams& p, const int32_t* __restrict__ ovf_list, int mode) {
   constexpr int kV = kHalfDim / 128;  // float4 per lane
   const int lane = threadIdx.x & 63, hl = lane & 31, hh = lane >> 5;
   const int wid = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -934,7 +983,6 @@ __global__ __launch_bounds__(256) void assign_rescore_half_kernel(AssignParams p
     const WorkItem w = p.work[mode == 2 ? ovf_list[it] : (p.work_idx ? p.work_idx[it] : it)];
     // an idle half (past the end, or an item of the other pass) repeats the work and writes nothing
     const bool active = it0 + hh < nitems && (mode == 0 || (mode == 1 ? w.n != -1 : w.n == -1));
-    const float* xr = p.x + (int64_t)w.row * p.dim;
     const float* car = RL >= 1 ? p.ca + (int64_t)seg_row(p.seg_ca, w.seg) * p.dim : nullptr;
     const float* cbr = RL >= 2 ? p.cb + (int64_t)seg_row(p.seg_cb, w.seg) * p.dim : nullptr;
     const bool screened = w.n >= 1 || w.n == -1;  // the screen wrote den_out for these rows
@@ -944,7 +992,7 @@ __global__ __launch_bounds__(256) void assign_rescore_half_kernel(AssignParams p
     for (int m = 0; m < kV; ++m) {
       const int i = hl + 32 * m;
       if (i < nv) {
-        float4 a = reinterpret_cast<const float4*>(xr)[i];
+        float4 a = load_row4<XF>(p.x, w.row, p.dim, i);
         if (RL >= 1) {
           const float4 c = reinterpret_cast<const float4*>(car)[i];
           a = make_float4(a.x - c.x, a.y - c.y, a.z - c.z, a.w - c.w);
@@ -1057,6 +1105,16 @@ __global__ __launch_bounds__(256) void assign_rescore_half_kernel(AssignParams p
     }
   }
 }
+template <int RL, bool NORM>
+__global__ __launch_bounds__(256) void assign_rescore_half_kernel(AssignParams p, const int32_t* __restrict__ ovf_list,
+                                                                  int mode) {
+  rescore_half_rows<RL, NORM, RQSID_X_F32>(p, ovf_list, mode);
+}
+template <int XF, int RL, bool NORM>
+__global__ __launch_bounds__(256) void assign_rescore_half_x16_kernel(AssignParams p, const int32_t* __restrict__ ovf_list,
+                                                                      int mode) {
+  rescore_half_rows<RL, NORM, XF>(p, ovf_list, mode);
+}
 
 // ---------------------------------------------------------------------------
 // fp32 re-screen of overflowing rows
@@ -1091,8 +1149,8 @@ __global__ __launch_bounds__(256) void overflow_list_kernel(AssignParams p, int3
   }
 }
 
-template <int RL, bool NORM>
-__global__ __launch_bounds__(256) void assign_rescreen_kernel(AssignParams p, const int32_t* __restrict__ ovf_list) {
+template <int RL, bool NORM, int XF>
+__device__ __forceinline__ void rescreen_rows(const AssignParams& p, const int32_t* __restrict__ ovf_list) {
   constexpr int kV = kHalfDim / 128;  // float4 per lane of a half
   const int lane = threadIdx.x & 63, hl = lane & 31, hh = lane >> 5;
   const int wid = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -1104,7 +1162,6 @@ __global__ __launch_bounds__(256) void assign_rescreen_kernel(AssignParams p, co
     const bool active = it0 + hh < nov;  // an idle half repeats its partner's item and writes nothing
     const int32_t idx = ovf_list[active ? it0 + hh : it0];
     WorkItem w = p.work[idx];
-    const float* xr = p.x + (int64_t)w.row * p.dim;
     const float* car = RL >= 1 ? p.ca + (int64_t)seg_row(p.seg_ca, w.seg) * p.dim : nullptr;
     const float* cbr = RL >= 2 ? p.cb + (int64_t)seg_row(p.seg_cb, w.seg) * p.dim : nullptr;
     // the row as the re-score rebuilds it (the reference's fp32 operation sequence)
@@ -1114,7 +1171,7 @@ __global__ __launch_bounds__(256) void assign_rescreen_kernel(AssignParams p, co
     for (int m = 0; m < kV; ++m) {
       const int i = hl + 32 * m;
       if (i < nv) {
-        float4 a = reinterpret_cast<const float4*>(xr)[i];
+        float4 a = load_row4<XF>(p.x, w.row, p.dim, i);
         if (RL >= 1) {
           const float4 c = reinterpret_cast<const float4*>(car)[i];
           a = make_float4(a.x - c.x, a.y - c.y, a.z - c.z, a.w - c.w);
@@ -1259,6 +1316,14 @@ __global__ __launch_bounds__(256) void assign_rescreen_kernel(AssignParams p, co
     }
   }
 }
+template <int RL, bool NORM>
+__global__ __launch_bounds__(256) void assign_rescreen_kernel(AssignParams p, const int32_t* __restrict__ ovf_list) {
+  rescreen_rows<RL, NORM, RQSID_X_F32>(p, ovf_list);
+}
+template <int XF, int RL, bool NORM>
+__global__ __launch_bounds__(256) void assign_rescreen_x16_kernel(AssignParams p, const int32_t* __restrict__ ovf_list) {
+  rescreen_rows<RL, NORM, XF>(p, ovf_list);
+}
 
 // tile -> segment map of the per-tile screen (one thread per tile, binary search of seg_tile_off)
 __global__ __launch_bounds__(256) void tile_seg128_kernel(const int32_t* __restrict__ seg_tile_off, int nseg,
@@ -1387,16 +1452,33 @@ __global__ __launch_bounds__(256) void centers_hi_kernel(const uint4* __restrict
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
-template <int NT, int S, bool T3, bool ONE, int CW = 1>
+// the screen build of a row format: assign_screen_kernel (fp32 rows) or assign_screen_x16_kernel
+template <int XF, int NT, int S, int RL, bool NORM, bool T3, bool ONE, int CW>
+constexpr auto screen_kernel() -> void (*)(AssignParams) {
+  if constexpr (XF == RQSID_X_F32) return assign_screen_kernel<NT, S, RL, NORM, T3, ONE, CW>;
+  else return assign_screen_x16_kernel<XF, NT, S, RL, NORM, T3, ONE>;
+}
+
+template <int NT, int S, bool T3, bool ONE, int CW = 1, int XF = RQSID_X_F32>
 void set_attrs(bool* ok) {
-  const int bytes = ScreenLayout<NT, S, T3, CW>::kMaxBytes;
-  const void* ks[] = {(const void*)assign_screen_kernel<NT, S, 0, false, T3, ONE, CW>,
-                      (const void*)assign_screen_kernel<NT, S, 1, false, T3, ONE, CW>,
-                      (const void*)assign_screen_kernel<NT, S, 1, true, T3, ONE, CW>,
-                      (const void*)assign_screen_kernel<NT, S, 2, false, T3, ONE, CW>,
-                      (const void*)assign_screen_kernel<NT, S, 2, true, T3, ONE, CW>};
+  const int bytes = ScreenLayout<NT, S, T3, CW, XF>::kMaxBytes;
+  const void* ks[] = {(const void*)screen_kernel<XF, NT, S, 0, false, T3, ONE, CW>(),
+                      (const void*)screen_kernel<XF, NT, S, 1, false, T3, ONE, CW>(),
+                      (const void*)screen_kernel<XF, NT, S, 1, true, T3, ONE, CW>(),
+                      (const void*)screen_kernel<XF, NT, S, 2, false, T3, ONE, CW>(),
+                      (const void*)screen_kernel<XF, NT, S, 2, true, T3, ONE, CW>()};
   for (const void* k : ks)
     if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) *ok = false;
+}
+// the per-tile forms of a 16-bit row format (no candidate split)
+template <int XF>
+void set_attrs_x16(bool* ok) {
+  set_attrs<4, 2, false, true, 1, XF>(ok);
+  set_attrs<8, 2, false, true, 1, XF>(ok);
+  set_attrs<4, 2, true, true, 1, XF>(ok);
+  set_attrs<4, 2, false, false, 1, XF>(ok);
+  set_attrs<8, 2, false, false, 1, XF>(ok);
+  set_attrs<4, 2, true, false, 1, XF>(ok);
 }
 
 // screen variant (tuning / A-B tests): 0 default (per level: see rqsid_assign); 1: per-tile kernel
@@ -1430,25 +1512,86 @@ int ensure_attrs() {
   set_attrs<4, 2, true, false>(&ok);
   set_attrs<8, kSplitS, false, true, 2>(&ok);
   set_attrs<4, kSplitS, true, true, 2>(&ok);
+  set_attrs_x16<RQSID_X_F16>(&ok);
+  set_attrs_x16<RQSID_X_BF16>(&ok);
   if (!ok) return fail(RQSID_E_LAUNCH, "assign: cannot raise the dynamic LDS limit");
   g_attr_done[dev] = true;
   return RQSID_OK;
 }
 
-template <int NT, int S, bool T3, bool ONE, int CW = 1>
+template <int NT, int S, bool T3, bool ONE, int CW = 1, int XF = RQSID_X_F32>
 void launch_screen(const AssignParams& p, int rl, bool norm, unsigned grid, hipStream_t st) {
-  const size_t lds = ScreenLayout<NT, S, T3, CW>::bytes(rl, p.dim);
+  const size_t lds = ScreenLayout<NT, S, T3, CW, XF>::bytes(rl, p.dim);
   const dim3 blk(256 * CW);
-  if (rl == 0) hipLaunchKernelGGL((assign_screen_kernel<NT, S, 0, false, T3, ONE, CW>), dim3(grid), blk, lds, st, p);
-  else if (rl == 1 && norm) hipLaunchKernelGGL((assign_screen_kernel<NT, S, 1, true, T3, ONE, CW>), dim3(grid), blk, lds, st, p);
-  else if (rl == 1) hipLaunchKernelGGL((assign_screen_kernel<NT, S, 1, false, T3, ONE, CW>), dim3(grid), blk, lds, st, p);
-  else if (norm) hipLaunchKernelGGL((assign_screen_kernel<NT, S, 2, true, T3, ONE, CW>), dim3(grid), blk, lds, st, p);
-  else hipLaunchKernelGGL((assign_screen_kernel<NT, S, 2, false, T3, ONE, CW>), dim3(grid), blk, lds, st, p);
+  if (rl == 0) hipLaunchKernelGGL((screen_kernel<XF, NT, S, 0, false, T3, ONE, CW>()), dim3(grid), blk, lds, st, p);
+  else if (rl == 1 && norm) hipLaunchKernelGGL((screen_kernel<XF, NT, S, 1, true, T3, ONE, CW>()), dim3(grid), blk, lds, st, p);
+  else if (rl == 1) hipLaunchKernelGGL((screen_kernel<XF, NT, S, 1, false, T3, ONE, CW>()), dim3(grid), blk, lds, st, p);
+  else if (norm) hipLaunchKernelGGL((screen_kernel<XF, NT, S, 2, true, T3, ONE, CW>()), dim3(grid), blk, lds, st, p);
+  else hipLaunchKernelGGL((screen_kernel<XF, NT, S, 2, false, T3, ONE, CW>()), dim3(grid), blk, lds, st, p);
 }
-template <int NT, int S, bool T3>
+template <int NT, int S, bool T3, int XF = RQSID_X_F32>
 void launch_screen2(const AssignParams& p, int rl, bool norm, unsigned grid, bool one, hipStream_t st) {
-  if (one) launch_screen<NT, S, T3, true>(p, rl, norm, grid, st);
-  else launch_screen<NT, S, T3, false>(p, rl, norm, grid, st);
+  if (one) launch_screen<NT, S, T3, true, 1, XF>(p, rl, norm, grid, st);
+  else launch_screen<NT, S, T3, false, 1, XF>(p, rl, norm, grid, st);
+}
+// 16-bit rows: always the per-tile form, with the NT / terms rule of the fp32 dispatch; segments wider than
+// one pass (3-term > 128 candidates, 1-term > 256) take the multi-pass form (no candidate split)
+template <int XF>
+void launch_screen_x16(const AssignParams& p, int rl, bool norm, unsigned grid, bool t3, int cand_count_max, bool legacy,
+                       hipStream_t st) {
+  if (t3) launch_screen2<4, 2, true, XF>(p, rl, norm, grid, !legacy && cand_count_max <= 128, st);
+  else if (cand_count_max <= 128) launch_screen2<4, 2, false, XF>(p, rl, norm, grid, !legacy, st);
+  else launch_screen2<8, 2, false, XF>(p, rl, norm, grid, !legacy && cand_count_max <= 256, st);
+}
+
+// the re-screen and the two re-score forms of a row format
+template <int XF, int RL, bool NORM>
+void launch_rescreen(const AssignParams& p, const int32_t* ovf_list, hipStream_t st) {
+  if constexpr (XF == RQSID_X_F32)
+    hipLaunchKernelGGL((assign_rescreen_kernel<RL, NORM>), dim3(2048), dim3(256), 0, st, p, ovf_list);
+  else
+    hipLaunchKernelGGL((assign_rescreen_x16_kernel<XF, RL, NORM>), dim3(2048), dim3(256), 0, st, p, ovf_list);
+}
+template <int XF, int RL, bool NORM>
+void launch_rescore_half(const AssignParams& p, const int32_t* ovf_list, int mode, dim3 g, hipStream_t st) {
+  if constexpr (XF == RQSID_X_F32)
+    hipLaunchKernelGGL((assign_rescore_half_kernel<RL, NORM>), g, dim3(256), 0, st, p, ovf_list, mode);
+  else
+    hipLaunchKernelGGL((assign_rescore_half_x16_kernel<XF, RL, NORM>), g, dim3(256), 0, st, p, ovf_list, mode);
+}
+template <int XF, int RL, bool NORM>
+void launch_rescore(const AssignParams& p, dim3 g, hipStream_t st) {
+  if constexpr (XF == RQSID_X_F32) hipLaunchKernelGGL((assign_rescore_kernel<RL, NORM>), g, dim3(256), 0, st, p);
+  else hipLaunchKernelGGL((assign_rescore_x16_kernel<XF, RL, NORM>), g, dim3(256), 0, st, p);
+}
+// the listed rows' exact fp64 re-score (ovf_list: the fp32 re-screen ran first)
+template <int XF, int RL, bool NORM>
+void launch_exact(const AssignParams& p, const int32_t* ovf_list, bool half, hipStream_t st) {
+  const dim3 g(4096);  // multiple of 8 (XCD-grouped work runs)
+  if (half && ovf_list) {
+    launch_rescore_half<XF, RL, NORM>(p, ovf_list, 1, g, st);
+    launch_rescore_half<XF, RL, NORM>(p, ovf_list, 2, g, st);
+  } else if (half) {
+    launch_rescore_half<XF, RL, NORM>(p, nullptr, 0, g, st);
+  } else {
+    launch_rescore<XF, RL, NORM>(p, g, st);
+  }
+}
+template <int XF>
+void launch_rescreen_xf(const AssignParams& p, int rl, bool norm, const int32_t* ovf_list, hipStream_t st) {
+  if (rl == 0) launch_rescreen<XF, 0, false>(p, ovf_list, st);
+  else if (rl == 1 && norm) launch_rescreen<XF, 1, true>(p, ovf_list, st);
+  else if (rl == 1) launch_rescreen<XF, 1, false>(p, ovf_list, st);
+  else if (norm) launch_rescreen<XF, 2, true>(p, ovf_list, st);
+  else launch_rescreen<XF, 2, false>(p, ovf_list, st);
+}
+template <int XF>
+void launch_exact_xf(const AssignParams& p, int rl, bool norm, const int32_t* ovf_list, bool half, hipStream_t st) {
+  if (rl == 0) launch_exact<XF, 0, false>(p, ovf_list, half, st);
+  else if (rl == 1 && norm) launch_exact<XF, 1, true>(p, ovf_list, half, st);
+  else if (rl == 1) launch_exact<XF, 1, false>(p, ovf_list, half, st);
+  else if (norm) launch_exact<XF, 2, true>(p, ovf_list, half, st);
+  else launch_exact<XF, 2, false>(p, ovf_list, half, st);
 }
 
 }  // namespace
@@ -1496,7 +1639,7 @@ int64_t rqsid_assign_workspace_bytes(int64_t n_rows) {
   return 256 + n * (int64_t)sizeof(WorkItem) + 3 * ((n * 4 + 255) / 256 * 256) + resident_desc_bytes(n);
 }
 
-int rqsid_assign(const float* x, int64_t n_rows, int32_t dim, const int32_t* row_index, int32_t n_segments,
+int rqsid_assign_x(const void* x, int32_t x_format, int64_t n_rows, int32_t dim, const int32_t* row_index, int32_t n_segments,
                  const int32_t* seg_row_off, const int32_t* seg_tile_off, int64_t max_tiles, const float* centers,
                  const uint16_t* c16, const uint16_t* c16_hi, const float* c_meta, int32_t n_centers,
                  const int32_t* cand_base,
@@ -1505,6 +1648,11 @@ int rqsid_assign(const float* x, int64_t n_rows, int32_t dim, const int32_t* row
                  const int32_t* seg_ca, const float* cb, const int32_t* seg_cb, const float* den_in,
                  float* den_out, int32_t* out_local, int32_t* out_global, int32_t screen_terms, void* workspace,
                  int64_t workspace_bytes, void* stream) {
+  if (x_format != RQSID_X_F32 && x_format != RQSID_X_F16 && x_format != RQSID_X_BF16)
+    return fail(RQSID_E_ARG, "assign: unknown x_format %d (RQSID_X_F32, RQSID_X_F16, RQSID_X_BF16)", x_format);
+  const bool x16 = x_format != RQSID_X_F32;
+  if (x16 && (reinterpret_cast<uintptr_t>(x) & 15))
+    return fail(RQSID_E_ARG, "assign: 16-bit rows need a 16-byte aligned x");
   if (dim <= 0 || dim % kChunk || dim > kMaxDim || n_rows < 0 || n_segments <= 0 || !seg_row_off ||
       !seg_tile_off || !centers || !c16 || !c_meta || !cand_base || !cand_count || (n_rows > 0 && (!out_local || !out_global)) ||
       n_centers <= 0 || cand_count_max < 0 || max_tiles < 0 || n_rows > INT32_MAX || res_levels < 0 ||
@@ -1521,7 +1669,7 @@ int rqsid_assign(const float* x, int64_t n_rows, int32_t dim, const int32_t* row
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
   AssignParams p{};
-  p.x = x;
+  p.x = static_cast<const float*>(x);  // 16-bit formats: read as such by the x16 kernels only
   p.dim = dim;
   p.row_index = row_index;
   p.n_segments = n_segments;
@@ -1584,19 +1732,21 @@ int rqsid_assign(const float* x, int64_t n_rows, int32_t dim, const int32_t* row
   // Variant 1 forces the per-tile kernel, variant 5 the stream forms (RQSID_STREAM_SHAPE).
   const int variant = screen_variant();
   const int shape = variant == 5 ? 0 : (variant == 0 && nt == 8 && !t3 && res_levels >= 1 ? 88 : -1);
-  const bool use_stream = stream_ok && shape >= 0 && variant != 6;
+  // 16-bit rows (x16): the per-tile form only; the streamed, producer/consumer, row- and centre-resident screens
+  // and the candidate split are fp32-row kernels, and RQSID_SCREEN_VARIANT values that name them are ignored
+  const bool use_stream = !x16 && stream_ok && shape >= 0 && variant != 6;
   // the centre-resident screen (assign_resident.hip): variant 6 forces it wherever it applies (1-term,
   // <= 256 candidates).  Not the default yet: measured L2 of the bench 8.0-9.1 ms against the ping-pong
   // form's 7.6 ms ('Centre-resident screen')
   const bool res_ok = resident_supported(dim, cand_count_max, t3, res_levels) && (int64_t)n_segments + 1 <= n_rows &&
                       (res_levels != 1 || !norm || den_out);
-  const bool use_res = res_ok && variant == 6;
+  const bool use_res = !x16 && res_ok && variant == 6;
   // the row-resident screen (assign_rows.hip): variant 8 forces it wherever it applies (1-term levels of
   // 512-d rows with <= 512 candidates)
   // default for 1-term residual levels wider than 256 candidates (the XL preset's 512-candidate last level:
   // 7.0 vs 14.8 ms for the candidate-split screen, profiles/r4_xl_rows_ab.txt); the 256-candidate PROD level
   // keeps the ping-pong form (7.4 vs 7.6-7.8 ms)
-  const bool use_rows = (variant == 8 || (variant == 0 && res_levels >= 1 && cand_count_max > 256)) &&
+  const bool use_rows = !x16 && (variant == 8 || (variant == 0 && res_levels >= 1 && cand_count_max > 256)) &&
                         rows_supported(dim, cand_count_max, t3, res_levels, norm) && (int64_t)n_segments + 1 <= n_rows;
   // the producer/consumer screen (assign_pc.hip): the default for the residual levels it covers (PROD level 1,
   // 3-term <= 128 candidates, and level 2, 1-term <= 256); RQSID_PC=0 keeps the older
@@ -1607,7 +1757,7 @@ int rqsid_assign(const float* x, int64_t n_rows, int32_t dim, const int32_t* row
                      pc_desc_bytes(n_rows, n_segments) <= resident_desc_bytes(n_rows);
   // (default: the 1-term levels; RQSID_PC=2 takes the 3-term ones too, RQSID_PC=0 none)
   const int pc_mode = pce ? atoi(pce) : 1;
-  const bool use_pc = pc_ok && (variant == 9 || (variant == 0 && (pc_mode >= 2 || (pc_mode == 1 && !t3))));
+  const bool use_pc = !x16 && pc_ok && (variant == 9 || (variant == 0 && (pc_mode >= 2 || (pc_mode == 1 && !t3))));
   if (use_pc) {
     // R-row tile offsets in the compact-list area, the tile map in the tile_seg slot, the tile descriptors in
     // the resident screen's descriptor area; a failed launch returns before the compaction and re-score
@@ -1654,14 +1804,15 @@ int rqsid_assign(const float* x, int64_t n_rows, int32_t dim, const int32_t* row
   // keeps the multi-pass screen for comparison
   const bool split = !legacy && variant != 7 && dim <= kSplitDim;
   if (use_pc || use_stream || use_res || use_rows) {
-  } else if (t3 && cand_count_max > 128 && split) launch_screen<4, kSplitS, true, true, 2>(p, res_levels, norm, grid, st);
+  } else if (x_format == RQSID_X_F16) launch_screen_x16<RQSID_X_F16>(p, res_levels, norm, grid, t3, cand_count_max, legacy, st);
+  else if (x_format == RQSID_X_BF16) launch_screen_x16<RQSID_X_BF16>(p, res_levels, norm, grid, t3, cand_count_max, legacy, st);
+  else if (t3 && cand_count_max > 128 && split) launch_screen<4, kSplitS, true, true, 2>(p, res_levels, norm, grid, st);
   else if (t3) launch_screen2<4, 2, true>(p, res_levels, norm, grid, !legacy && cand_count_max <= 128, st);
   else if (cand_count_max <= 128) launch_screen2<4, 2, false>(p, res_levels, norm, grid, !legacy, st);
   else if (cand_count_max <= 256) launch_screen2<8, 2, false>(p, res_levels, norm, grid, !legacy, st);
   else if (cand_count_max <= 512 && split) launch_screen<8, kSplitS, false, true, 2>(p, res_levels, norm, grid, st);
   else launch_screen<8, 2, false, false>(p, res_levels, norm, grid, st);
   if ((rc = check_launch("assign_screen"))) return rc;
-  const dim3 g(4096);  // multiple of 8 (XCD-grouped work runs)
   // two rows per wave for rows of <= 512 dims (RQSID_RESCORE_FULL=1: one row per wave, for A/B)
   const char* ef = getenv("RQSID_RESCORE_FULL");
   const bool half = dim <= kHalfDim && !(ef && atoi(ef));
@@ -1672,32 +1823,14 @@ int rqsid_assign(const float* x, int64_t n_rows, int32_t dim, const int32_t* row
     ovf_list = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(work_idx) + (n_rows * 4 + 255) / 256 * 256 +
                                           resident_desc_bytes(n_rows));
     hipLaunchKernelGGL(overflow_list_kernel, dim3(grid_cap(cdiv(n_rows, 256), 1024)), dim3(256), 0, st, p, ovf_list);
-#define RQ_RSC(RL, NORM) hipLaunchKernelGGL((assign_rescreen_kernel<RL, NORM>), dim3(2048), dim3(256), 0, st, p, ovf_list)
-    if (res_levels == 0) RQ_RSC(0, false);
-    else if (res_levels == 1 && norm) RQ_RSC(1, true);
-    else if (res_levels == 1) RQ_RSC(1, false);
-    else if (norm) RQ_RSC(2, true);
-    else RQ_RSC(2, false);
-#undef RQ_RSC
+    if (x_format == RQSID_X_F16) launch_rescreen_xf<RQSID_X_F16>(p, res_levels, norm, ovf_list, st);
+    else if (x_format == RQSID_X_BF16) launch_rescreen_xf<RQSID_X_BF16>(p, res_levels, norm, ovf_list, st);
+    else launch_rescreen_xf<RQSID_X_F32>(p, res_levels, norm, ovf_list, st);
     if ((rc = check_launch("assign_rescreen"))) return rc;
   }
-#define RQ_RS(RL, NORM)                                                                                       \
-  do {                                                                                                        \
-    if (half && ovf_list) {                                                                                   \
-      hipLaunchKernelGGL((assign_rescore_half_kernel<RL, NORM>), g, dim3(256), 0, st, p, ovf_list, 1);          \
-      hipLaunchKernelGGL((assign_rescore_half_kernel<RL, NORM>), g, dim3(256), 0, st, p, ovf_list, 2);          \
-    } else if (half) {                                                                                        \
-      hipLaunchKernelGGL((assign_rescore_half_kernel<RL, NORM>), g, dim3(256), 0, st, p, (const int32_t*)nullptr, 0); \
-    } else {                                                                                                  \
-      hipLaunchKernelGGL((assign_rescore_kernel<RL, NORM>), g, dim3(256), 0, st, p);                          \
-    }                                                                                                         \
-  } while (0)
-  if (res_levels == 0) RQ_RS(0, false);
-  else if (res_levels == 1 && norm) RQ_RS(1, true);
-  else if (res_levels == 1) RQ_RS(1, false);
-  else if (norm) RQ_RS(2, true);
-  else RQ_RS(2, false);
-#undef RQ_RS
+  if (x_format == RQSID_X_F16) launch_exact_xf<RQSID_X_F16>(p, res_levels, norm, ovf_list, half, st);
+  else if (x_format == RQSID_X_BF16) launch_exact_xf<RQSID_X_BF16>(p, res_levels, norm, ovf_list, half, st);
+  else launch_exact_xf<RQSID_X_F32>(p, res_levels, norm, ovf_list, half, st);
   if ((rc = check_launch("assign_rescore"))) return rc;
   if (use_res) {
     // the resident screen's role waits are capped (assign_resident.hip): a wave that gave up waiting
@@ -1708,6 +1841,21 @@ int rqsid_assign(const float* x, int64_t n_rows, int32_t dim, const int32_t* row
     if (err) return fail(RQSID_E_LAUNCH, "assign: a resident-screen wait reached its spin cap (error word %d)", err);
   }
   return RQSID_OK;
+}
+
+int rqsid_assign(const float* x, int64_t n_rows, int32_t dim, const int32_t* row_index, int32_t n_segments,
+                 const int32_t* seg_row_off, const int32_t* seg_tile_off, int64_t max_tiles, const float* centers,
+                 const uint16_t* c16, const uint16_t* c16_hi, const float* c_meta, int32_t n_centers,
+                 const int32_t* cand_base,
+                 const int32_t* cand_count, int32_t cand_count_max, const int32_t* cand_idx,
+                 const int32_t* cand_lid, const uint8_t* seg_flags, int32_t res_levels, int32_t res_normalize, const float* ca,
+                 const int32_t* seg_ca, const float* cb, const int32_t* seg_cb, const float* den_in,
+                 float* den_out, int32_t* out_local, int32_t* out_global, int32_t screen_terms, void* workspace,
+                 int64_t workspace_bytes, void* stream) {
+  return rqsid_assign_x(x, RQSID_X_F32, n_rows, dim, row_index, n_segments, seg_row_off, seg_tile_off, max_tiles, centers,
+                        c16, c16_hi, c_meta, n_centers, cand_base, cand_count, cand_count_max, cand_idx, cand_lid, seg_flags,
+                        res_levels, res_normalize, ca, seg_ca, cb, seg_cb, den_in, den_out, out_local, out_global,
+                        screen_terms, workspace, workspace_bytes, stream);
 }
 
 #ifdef RQSID_STAMPS

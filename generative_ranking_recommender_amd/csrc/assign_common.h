@@ -25,6 +25,15 @@ constexpr int kXWaveBytes = kRowsPerWave * 128;    // 4 KiB: 32 rows x 32 fp32 d
 constexpr int kXStage = kWaves * kXWaveBytes;      // 16 KiB
 constexpr int kMaxDim = 1024;
 
+// Row formats of rqsid_assign_x (XF template argument = RQSID_X_*).  16-bit rows: a 32-dim chunk is 64 B
+// per row, so a wave's 32 rows take two DMA ops instead of four and the row image has the shape of the
+// centre hi image (64-B rows, 16-B slot q at q ^ ((row >> 2) & 3), one 16-B LDS read per lane per k-step).
+constexpr int x_row_bytes(int xf) { return xf == RQSID_X_F32 ? 4 * kChunk : 2 * kChunk; }  // one chunk of one row
+constexpr int x_wave_bytes(int xf) { return kRowsPerWave * x_row_bytes(xf); }
+constexpr int x_stage_bytes(int xf) { return kWaves * x_wave_bytes(xf); }
+constexpr int x_wave_ops(int xf) { return x_wave_bytes(xf) / 1024; }  // 1-KiB DMA ops per wave per chunk
+static_assert(x_wave_bytes(RQSID_X_F32) == kXWaveBytes && x_stage_bytes(RQSID_X_F32) == kXStage, "fp32 row image");
+
 constexpr int kListPerHalf = 4;             // candidates a lane half can list exactly
 constexpr int kMaxList = 2 * kListPerHalf;   // per row
 struct WorkItem {
@@ -376,6 +385,48 @@ __device__ __forceinline__ float sub_f16(float v, h2 hh) {
   else
     asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(d) : "v"(hh), "v"(v));
   return d;
+}
+
+// Two 16-bit row elements (one dword, even element in the low half) widened to fp32, exactly, with integer
+// moves and one fp32 multiply, so the result does not depend on the wave's FP16 denormal mode: the screens
+// run with FP16 denormals flushed (assign_screen_kernel), where v_cvt_f32_f16 would read a subnormal fp16
+// row element as 0 and the measured |v - vh| would miss it.
+//   bf16: the fp32 with the same upper 16 bits.
+//   fp16: |h| << 13 is the fp32 whose value is |h| 2^-112 (fp16 exponent field e, also e = 0, lands in the
+//         fp32 exponent field; fp32 denormals are on), times 2^112 (exact), sign copied in.  Inf / NaN
+//         (e = 31) widen to finite values >= 65536 in the screen form (INFNAN false): like every value
+//         beyond the fp16 range they make the row's bound infinite (row_frag), and the re-screen and the
+//         re-score (INFNAN true) widen them to inf / NaN proper.
+template <int XF, bool INFNAN>
+__device__ __forceinline__ void widen2(uint32_t w, float& lo, float& hi) {
+  static_assert(XF == RQSID_X_F16 || XF == RQSID_X_BF16, "16-bit row formats");
+  if (XF == RQSID_X_BF16) {
+    lo = __uint_as_float(w << 16);
+    hi = __uint_as_float(w & 0xFFFF0000u);
+  } else {
+    const uint32_t sl = w << 16;
+    uint32_t al = (w << 13) & 0x0FFFE000u, ah = (w >> 3) & 0x0FFFE000u;
+    float fl = __uint_as_float(al) * 0x1p112f, fh = __uint_as_float(ah) * 0x1p112f;
+    if (INFNAN) {
+      fl = al >= 0x0F800000u ? __uint_as_float(__float_as_uint(fl) | 0x7F800000u) : fl;
+      fh = ah >= 0x0F800000u ? __uint_as_float(__float_as_uint(fh) | 0x7F800000u) : fh;
+    }
+    lo = __uint_as_float((__float_as_uint(fl) & 0x7FFFFFFFu) | (sl & 0x80000000u));
+    hi = __uint_as_float((__float_as_uint(fh) & 0x7FFFFFFFu) | (w & 0x80000000u));
+  }
+}
+// elements 4 i .. 4 i + 3 of a row (rows are 16-byte aligned: dim % 32 == 0 and an aligned base)
+template <int XF>
+__device__ __forceinline__ float4 load_row4(const float* x, int64_t row, int dim, int i) {
+  if constexpr (XF == RQSID_X_F32) {
+    return reinterpret_cast<const float4*>(x + row * dim)[i];
+  } else {
+    const uint2 w = reinterpret_cast<const uint2*>(reinterpret_cast<const uint16_t*>(x) + row * dim)[i];
+    float4 a;
+    widen2<XF, true>(w.x, a.x, a.y);
+    widen2<XF, true>(w.y, a.z, a.w);
+    return a;
+  }
 }
 
 // One 16-dim k-step of a row fragment: lane (r, h) holds dims d0 .. d0+7 of its row's vector

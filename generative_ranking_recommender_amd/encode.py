@@ -2,7 +2,8 @@
 
 One ``RQEncoder`` holds the trained codebooks of every level, already prepared
 for ``rqsid_assign`` (fp16 copy, norms, candidate lists), and turns an fp32
-[N, D] device matrix into int32 [N, L] semantic IDs with no host round trip.
+(or fp16 / bf16) [N, D] device matrix into int32 [N, L] semantic IDs with no
+host round trip.
 
 Level semantics:
 
@@ -88,6 +89,7 @@ class RQEncoder:
         self._ws = None
         self._bws = {}  # n_segments -> reusable rqsid_bucket workspace (sticky error word)
         self.last_rescored = []
+        self.last_row_format = "f32"
         self.force_materialized = False
 
     def _workspace(self, n):
@@ -135,15 +137,21 @@ class RQEncoder:
         return True
 
     def encode(self, x: torch.Tensor, count_rescored: bool = False, check: Optional[bool] = None) -> torch.Tensor:
-        """x: f32 [N, D] on the device -> int32 [N, L] semantic IDs (a transposed view of the
-        level-major [L, N] buffer the kernels write; no copy).  ``check`` (default: on unless the stream is
+        """x: f32 (or, read natively on the fused path, f16 / bf16) [N, D] on the device -> int32 [N, L]
+        semantic IDs (a transposed view of the level-major [L, N] buffer the kernels write; no copy).
+        ``last_row_format`` ("f32", "f16", "bf16") records the row format the kernels read.  ``check`` (default: on unless the stream is
         being captured into a graph): read the device error words after the call (one host sync) and raise
         if a counter-driven list write was dropped; a captured step checks with ``check_errors()``."""
         if check is None:
             check = not torch.cuda.is_current_stream_capturing()
         if x.dim() != 2 or x.shape[1] != self.dim:
             raise ValueError(f"Input dimension {x.shape[-1]} does not match config embedding_dim {self.dim}")
-        x = x.float().contiguous()
+        # 16-bit rows stay as they are on the fused path (every level reads x itself, rqsid_assign_x); the
+        # materialised path writes fp32 residual matrices anyway and upcasts once, like any other dtype
+        if not (self.fused and x.dtype in (torch.float16, torch.bfloat16)):
+            x = x.float()
+        x = x.contiguous()
+        self.last_row_format = ops.ROW_FORMAT_NAMES[x.dtype]
         if self.L == 2:
             raise IndexError("list index out of range")  # reference: all_cluster_ids[-2] with one level
         n = x.shape[0]

@@ -812,13 +812,16 @@ class HierarchicalRQKMeans:
         cfg = self.config
         if X.shape[1] != cfg.embedding_dim:
             raise ValueError(f"Input dimension {X.shape[1]} does not match config embedding_dim {cfg.embedding_dim}")
+        # fp16 rows (the reader's format when any layer_clusters > 512, io.py) cross to the device as fp16: half
+        # the copy, and where the encoder is fused the kernels read them as they are (widening is lossless)
+        row_dtype = np.float16 if X.dtype == np.float16 else np.float32
         if self.group is not None:
             from .distributed import Comm, shard_bounds
             comm = Comm(self.group)
             s0, s1 = shard_bounds(len(X), comm.rank, comm.world)
-            x = torch.from_numpy(np.ascontiguousarray(X[s0:s1], dtype=np.float32)).to(self.device)
+            x = torch.from_numpy(np.ascontiguousarray(X[s0:s1], dtype=row_dtype)).to(self.device)
             return self.gather_ids(self.encode_shard(x, reference_quirks)).cpu().numpy().astype(np.int64)
-        x = torch.from_numpy(np.ascontiguousarray(X, dtype=np.float32)).to(self.device)
+        x = torch.from_numpy(np.ascontiguousarray(X, dtype=row_dtype)).to(self.device)
         return self.encode_shard(x, reference_quirks).cpu().numpy().astype(np.int64)
 
     def _encoder(self, reference_quirks: bool):
@@ -857,7 +860,8 @@ class HierarchicalRQKMeans:
 
     def encode_shard(self, x: torch.Tensor, reference_quirks: bool = False) -> torch.Tensor:
         """Encode device-resident rows (this rank's shard): int32 [n, L] on the device.  The hot path of
-        ``predict`` and of bench.py (no host copies, no collective)."""
+        ``predict`` and of bench.py (no host copies, no collective).  float16 / bfloat16 rows pass through to
+        the encoder as they are (``RQEncoder.encode``)."""
         L = len(self.config.layer_clusters)
         if x.shape[0] == 0:
             return torch.zeros((0, L), dtype=torch.int32, device=self.device)

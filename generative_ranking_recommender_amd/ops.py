@@ -47,6 +47,9 @@ def centroid_tile_rows() -> int:
 
 
 kMaxList = 8  # candidates a screen can list per row (assign_common.h)
+# row dtypes rqsid_assign reads -> RQSID_X_* (include/rqsid.h) and the name RQEncoder.last_row_format reports
+ROW_FORMATS = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
+ROW_FORMAT_NAMES = {torch.float32: "f32", torch.float16: "f16", torch.bfloat16: "bf16"}
 # the 1-term streamed screens gather centre pieces from a hi-only copy of the table (RQSID_HI_TABLE=0: from the
 # interleaved table, for A/B); read once at import
 HI_TABLE = __import__("os").environ.get("RQSID_HI_TABLE", "1") != "0"
@@ -267,8 +270,12 @@ def assign(x: torch.Tensor, pc: PreparedCenters, buckets: Buckets, cand: Candida
            workspace: Optional[AssignWorkspace] = None, fused: Optional[FusedResidual] = None,
            screen_terms: int = 0):
     """Exact segmented argmin. Returns (local i32[N], global i32[N]).  ``screen_terms`` (0 auto, 1, 3)
-    only changes how much work the exact answer takes."""
+    only changes how much work the exact answer takes.  ``x``: float32, or float16 / bfloat16 rows, which
+    the kernels read as they are (rqsid_assign_x: no fp32 copy; IDs bit-identical to ``x.float()``)."""
     _require_device(x, pc.centers, cand.base, cand.count, cand.idx, cand.flags)
+    x_format = ROW_FORMATS.get(x.dtype)
+    if x_format is None:
+        raise ValueError(f"rqsid_assign reads float32, float16 or bfloat16 rows, not {x.dtype}")
     n, d = x.shape
     if d != pc.centers.shape[1]:
         raise ValueError(f"dimension mismatch: x has {d}, centres {pc.centers.shape[1]}")
@@ -282,8 +289,10 @@ def assign(x: torch.Tensor, pc: PreparedCenters, buckets: Buckets, cand: Candida
     f = fused
     if f is not None:
         _require_device(f.ca, f.seg_ca, f.cb, f.seg_cb, f.den_in, f.den_out)
-    _lib.check(lib().rqsid_assign(
-        _ptr(x), n, d, _ptr(buckets.row_index), buckets.n_segments, _ptr(buckets.seg_row_off),
+    fn, head, what = (lib().rqsid_assign, (), "rqsid_assign") if x_format == 0 else \
+        (lib().rqsid_assign_x, (x_format,), "rqsid_assign_x")
+    _lib.check(fn(
+        _ptr(x), *head, n, d, _ptr(buckets.row_index), buckets.n_segments, _ptr(buckets.seg_row_off),
         _ptr(buckets.seg_tile_off), buckets.max_tiles,
         _ptr(pc.centers), _ptr(pc.c16), _ptr(pc.c16h), _ptr(pc.meta), pc.k,
         _ptr(cand.base), _ptr(cand.count), cand.count_max, _ptr(cand.idx), _ptr(cand.lid), _ptr(cand.flags),
@@ -292,7 +301,7 @@ def assign(x: torch.Tensor, pc: PreparedCenters, buckets: Buckets, cand: Candida
         None if f is None else _ptr(f.cb), None if f is None else _ptr(f.seg_cb),
         None if f is None else _ptr(f.den_in), None if f is None else _ptr(f.den_out),
         _ptr(out_local), _ptr(out_global), int(screen_terms), _ptr(workspace.buf), workspace.bytes, _stream()),
-        "rqsid_assign")
+        what)
     return out_local, out_global
 
 

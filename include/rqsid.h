@@ -17,7 +17,8 @@
  *    no host synchronisation, graph-capturable;
  *  - return 0 on success, a negative RQSID_E* code otherwise; the text of the
  *    last error of the calling thread is in rqsid_last_error();
- *  - matrices are row-major fp32 [rows][dim]; dim must be a multiple of 32.
+ *  - matrices are row-major [rows][dim], fp32 unless an entry point says otherwise (rqsid_assign_x also
+ *    takes the row matrix as IEEE fp16 or bfloat16); dim must be a multiple of 32.
  */
 #ifndef RQSID_H
 #define RQSID_H
@@ -34,6 +35,11 @@ extern "C" {
 
 /* segment flags (rqsid_assign seg_flags[s]) */
 #define RQSID_SEG_PENALTY 1u  /* empty allowed set: argmin over ALL centres of fl(d + 10000) */
+
+/* row formats (rqsid_assign_x x_format) */
+#define RQSID_X_F32 0   /* float */
+#define RQSID_X_F16 1   /* IEEE binary16 */
+#define RQSID_X_BF16 2  /* bfloat16 */
 
 int rqsid_version(void);
 const char* rqsid_last_error(void);
@@ -136,6 +142,28 @@ int rqsid_assign(const float* x, int64_t n_rows, int32_t dim, const int32_t* row
                  const float* den_in, float* den_out,
                  int32_t* out_local, int32_t* out_global, int32_t screen_terms,
                  void* workspace, int64_t workspace_bytes, void* stream);
+/* rqsid_assign with the row matrix x in the format x_format (RQSID_X_*); every other argument as above, and the
+ * same workspace query.  RQSID_X_F32 is rqsid_assign itself (the same dispatch).  RQSID_X_F16 / RQSID_X_BF16
+ * read 16-bit rows [rows][dim] (x 16-byte aligned) with no fp32 copy of them anywhere: the screen streams
+ * 64-B row pieces, widens each element to fp32 (lossless) as it leaves LDS and runs the fp32 operation
+ * sequence from there, and the re-screen / re-score widen as they load, so the IDs (and den_out) are
+ * bit-identical to rqsid_assign on the widened rows.  16-bit rows always take the per-tile screen (multi-pass
+ * for segments wider than 256 candidates, or 128 with 3 terms): the streamed, producer/consumer, row- and
+ * centre-resident screens and the candidate split are fp32-row kernels, so RQSID_SCREEN_VARIANT values that
+ * name them (5, 6, 7, 8, 9) and RQSID_PC are ignored for these formats.  An unknown x_format is
+ * RQSID_E_ARG before any launch. */
+int rqsid_assign_x(const void* x, int32_t x_format, int64_t n_rows, int32_t dim, const int32_t* row_index,
+                   int32_t n_segments, const int32_t* seg_row_off, const int32_t* seg_tile_off,
+                   int64_t max_tiles,
+                   const float* centers, const uint16_t* c16, const uint16_t* c16_hi, const float* c_meta,
+                   int32_t n_centers,
+                   const int32_t* cand_base, const int32_t* cand_count, int32_t cand_count_max,
+                   const int32_t* cand_idx, const int32_t* cand_lid, const uint8_t* seg_flags,
+                   int32_t res_levels, int32_t res_normalize,
+                   const float* ca, const int32_t* seg_ca, const float* cb, const int32_t* seg_cb,
+                   const float* den_in, float* den_out,
+                   int32_t* out_local, int32_t* out_global, int32_t screen_terms,
+                   void* workspace, int64_t workspace_bytes, void* stream);
 
 /* Residual r = x - c[center_id[row]]; with normalize != 0 each dimension group
  * g is divided by (||r_g|| + 1e-8).  Replaces _compute_residuals_with_centers
