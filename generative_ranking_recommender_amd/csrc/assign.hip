@@ -102,6 +102,7 @@ __global__ void centers_scale_kernel(float* __restrict__ scale) {
 #endif
 
 constexpr int kSplitDim = 512;  // widest row of the candidate-split form
+static_assert(kSplitDim == kPlanSplitDim, "assign_plan.h constants");
 // CW candidate groups (CW > 1: the candidate-split form, 4 CW waves, see assign_screen_kernel)
 template <int NT, int S, bool T3, int CW = 1, int XF = RQSID_X_F32>
 struct ScreenLayout {
@@ -952,6 +953,7 @@ __global__ __launch_bounds__(256) void assign_rescore_x16_kernel(AssignParams p)
 // re-score is bound by its dependent-load chain (item -> row, residual rows -> candidate rows), not by
 // bytes, and a wave now carries two chains at the same register count.
 constexpr int kHalfDim = 512;
+static_assert(kHalfDim == kPlanHalfDim, "assign_plan.h constants");
 __device__ __forceinline__ double half_sum(double v) {
 #pragma unroll
   for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o);
@@ -1470,9 +1472,10 @@ void set_attrs(bool* ok) {
   for (const void* k : ks)
     if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) *ok = false;
 }
-// the per-tile forms of a 16-bit row format (no candidate split)
+// the per-tile forms every row format has (launch_tile_screen): NT4 1-term, NT8 1-term, NT4 3-term, each with
+// the single-pass and the multi-pass epilogue
 template <int XF>
-void set_attrs_x16(bool* ok) {
+void set_attrs_xf(bool* ok) {
   set_attrs<4, 2, false, true, 1, XF>(ok);
   set_attrs<8, 2, false, true, 1, XF>(ok);
   set_attrs<4, 2, true, true, 1, XF>(ok);
@@ -1481,39 +1484,17 @@ void set_attrs_x16(bool* ok) {
   set_attrs<4, 2, true, false, 1, XF>(ok);
 }
 
-// screen variant (tuning / A-B tests): 0 default (per level: see rqsid_assign); 1: per-tile kernel
-// only; 2: per-tile kernel with the multi-sweep list epilogue on single-pass segments; 5: the
-// persistent streamed kernels (assign_stream.hip, RQSID_STREAM_SHAPE) where they apply; 6: the
-// centre-resident screen; 7: no candidate split; 8: the row-resident screen (assign_rows.hip,
-// RQSID_ROWS_SHAPE)
-int screen_variant() {  // read per call: tests switch it within one process
-  const char* e = getenv("RQSID_SCREEN_VARIANT");
-  return e ? atoi(e) : 0;
-}
-
-// ring depth of the candidate-split form (one block per CU).  S = 3 (96 KiB in flight per CU instead of
-// 48) measured no faster on the XL levels (L2 15.3 vs 14.8 ms), so the smaller ring stays
-#ifndef RQSID_SPLIT_S
-#define RQSID_SPLIT_S 2
-#endif
-constexpr int kSplitS = RQSID_SPLIT_S;
-
 bool g_attr_done[kMaxDevices] = {};
 int ensure_attrs() {
   const int dev = current_device();
   if (dev < 0) return fail(RQSID_E_LAUNCH, "assign: hipGetDevice failed");
   if (g_attr_done[dev]) return RQSID_OK;
   bool ok = true;
-  set_attrs<4, 2, false, true>(&ok);
-  set_attrs<8, 2, false, true>(&ok);
-  set_attrs<4, 2, true, true>(&ok);
-  set_attrs<4, 2, false, false>(&ok);
-  set_attrs<8, 2, false, false>(&ok);
-  set_attrs<4, 2, true, false>(&ok);
-  set_attrs<8, kSplitS, false, true, 2>(&ok);
+  set_attrs_xf<RQSID_X_F32>(&ok);
+  set_attrs_xf<RQSID_X_F16>(&ok);
+  set_attrs_xf<RQSID_X_BF16>(&ok);
+  set_attrs<8, kSplitS, false, true, 2>(&ok);  // the candidate split: fp32 rows only
   set_attrs<4, kSplitS, true, true, 2>(&ok);
-  set_attrs_x16<RQSID_X_F16>(&ok);
-  set_attrs_x16<RQSID_X_BF16>(&ok);
   if (!ok) return fail(RQSID_E_LAUNCH, "assign: cannot raise the dynamic LDS limit");
   g_attr_done[dev] = true;
   return RQSID_OK;
@@ -1522,26 +1503,25 @@ int ensure_attrs() {
 template <int NT, int S, bool T3, bool ONE, int CW = 1, int XF = RQSID_X_F32>
 void launch_screen(const AssignParams& p, int rl, bool norm, unsigned grid, hipStream_t st) {
   const size_t lds = ScreenLayout<NT, S, T3, CW, XF>::bytes(rl, p.dim);
-  const dim3 blk(256 * CW);
-  if (rl == 0) hipLaunchKernelGGL((screen_kernel<XF, NT, S, 0, false, T3, ONE, CW>()), dim3(grid), blk, lds, st, p);
-  else if (rl == 1 && norm) hipLaunchKernelGGL((screen_kernel<XF, NT, S, 1, true, T3, ONE, CW>()), dim3(grid), blk, lds, st, p);
-  else if (rl == 1) hipLaunchKernelGGL((screen_kernel<XF, NT, S, 1, false, T3, ONE, CW>()), dim3(grid), blk, lds, st, p);
-  else if (norm) hipLaunchKernelGGL((screen_kernel<XF, NT, S, 2, true, T3, ONE, CW>()), dim3(grid), blk, lds, st, p);
-  else hipLaunchKernelGGL((screen_kernel<XF, NT, S, 2, false, T3, ONE, CW>()), dim3(grid), blk, lds, st, p);
+  dispatch_rl_norm(rl, norm, [&](auto RL, auto NORM) {
+    hipLaunchKernelGGL((screen_kernel<XF, NT, S, RL(), NORM(), T3, ONE, CW>()), dim3(grid), dim3(256 * CW), lds, st, p);
+  });
 }
-template <int NT, int S, bool T3, int XF = RQSID_X_F32>
+template <int NT, int S, bool T3, int XF>
 void launch_screen2(const AssignParams& p, int rl, bool norm, unsigned grid, bool one, hipStream_t st) {
   if (one) launch_screen<NT, S, T3, true, 1, XF>(p, rl, norm, grid, st);
   else launch_screen<NT, S, T3, false, 1, XF>(p, rl, norm, grid, st);
 }
-// 16-bit rows: always the per-tile form, with the NT / terms rule of the fp32 dispatch; segments wider than
-// one pass (3-term > 128 candidates, 1-term > 256) take the multi-pass form (no candidate split)
+// the per-tile build the plan names (the candidate split has fp32-row builds only, and the plan knows it)
 template <int XF>
-void launch_screen_x16(const AssignParams& p, int rl, bool norm, unsigned grid, bool t3, int cand_count_max, bool legacy,
-                       hipStream_t st) {
-  if (t3) launch_screen2<4, 2, true, XF>(p, rl, norm, grid, !legacy && cand_count_max <= 128, st);
-  else if (cand_count_max <= 128) launch_screen2<4, 2, false, XF>(p, rl, norm, grid, !legacy, st);
-  else launch_screen2<8, 2, false, XF>(p, rl, norm, grid, !legacy && cand_count_max <= 256, st);
+void launch_tile_screen(const AssignParams& p, const AssignPlan& plan, int rl, bool norm, unsigned grid, hipStream_t st) {
+  if constexpr (XF == RQSID_X_F32) {
+    if (plan.cw == 2 && plan.t3) return launch_screen<4, kSplitS, true, true, 2>(p, rl, norm, grid, st);
+    if (plan.cw == 2) return launch_screen<8, kSplitS, false, true, 2>(p, rl, norm, grid, st);
+  }
+  if (plan.t3) launch_screen2<4, 2, true, XF>(p, rl, norm, grid, plan.one, st);
+  else if (plan.nt == 4) launch_screen2<4, 2, false, XF>(p, rl, norm, grid, plan.one, st);
+  else launch_screen2<8, 2, false, XF>(p, rl, norm, grid, plan.one, st);
 }
 
 // the re-screen and the two re-score forms of a row format
@@ -1577,21 +1557,23 @@ void launch_exact(const AssignParams& p, const int32_t* ovf_list, bool half, hip
     launch_rescore<XF, RL, NORM>(p, g, st);
   }
 }
-template <int XF>
-void launch_rescreen_xf(const AssignParams& p, int rl, bool norm, const int32_t* ovf_list, hipStream_t st) {
-  if (rl == 0) launch_rescreen<XF, 0, false>(p, ovf_list, st);
-  else if (rl == 1 && norm) launch_rescreen<XF, 1, true>(p, ovf_list, st);
-  else if (rl == 1) launch_rescreen<XF, 1, false>(p, ovf_list, st);
-  else if (norm) launch_rescreen<XF, 2, true>(p, ovf_list, st);
-  else launch_rescreen<XF, 2, false>(p, ovf_list, st);
+
+int env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : dflt;
 }
-template <int XF>
-void launch_exact_xf(const AssignParams& p, int rl, bool norm, const int32_t* ovf_list, bool half, hipStream_t st) {
-  if (rl == 0) launch_exact<XF, 0, false>(p, ovf_list, half, st);
-  else if (rl == 1 && norm) launch_exact<XF, 1, true>(p, ovf_list, half, st);
-  else if (rl == 1) launch_exact<XF, 1, false>(p, ovf_list, half, st);
-  else if (norm) launch_exact<XF, 2, true>(p, ovf_list, half, st);
-  else launch_exact<XF, 2, false>(p, ovf_list, half, st);
+// the one place the assign path reads the environment; once per call (tests switch variables within one process)
+AssignEnv read_assign_env() {
+  AssignEnv e;
+  e.screen_variant = env_int("RQSID_SCREEN_VARIANT", e.screen_variant);
+  e.pc = env_int("RQSID_PC", e.pc);
+  e.pcw = env_int("RQSID_PCW", e.pcw);
+  e.stream_shape = env_int("RQSID_STREAM_SHAPE", e.stream_shape);
+  e.rows_shape = env_int("RQSID_ROWS_SHAPE", e.rows_shape);
+  e.rescore_full = env_int("RQSID_RESCORE_FULL", e.rescore_full);
+  e.no_rescreen = env_int("RQSID_NO_RESCREEN", e.no_rescreen);
+  e.test_force_spin_cap = env_int("RQSID_TEST_FORCE_SPIN_CAP", e.test_force_spin_cap);
+  return e;
 }
 
 }  // namespace
@@ -1631,13 +1613,8 @@ int rqsid_prepare_centers_hi(const uint16_t* c16, int64_t k, int32_t dim, uint16
 
 int32_t rqsid_assign_tile_rows(void) { return kTileRows; }
 
-// workspace: [0,256) counters and store sinks | WorkItem[n_rows] | tile->segment map i32[n_rows]
-// (tiles <= rows) | compact row list i32[n_rows] (resident screen: 32-row tile offsets per segment) |
-// resident screen tile descriptors int4[n_rows] | overflow item list i32[n_rows] (fp32 re-screen)
-int64_t rqsid_assign_workspace_bytes(int64_t n_rows) {
-  const int64_t n = n_rows > 0 ? n_rows : 0;
-  return 256 + n * (int64_t)sizeof(WorkItem) + 3 * ((n * 4 + 255) / 256 * 256) + resident_desc_bytes(n);
-}
+// (the workspace's areas: AssignWorkspaceMap, assign_plan.h)
+int64_t rqsid_assign_workspace_bytes(int64_t n_rows) { return AssignWorkspaceMap(n_rows).total_bytes; }
 
 int rqsid_assign_x(const void* x, int32_t x_format, int64_t n_rows, int32_t dim, const int32_t* row_index, int32_t n_segments,
                  const int32_t* seg_row_off, const int32_t* seg_tile_off, int64_t max_tiles, const float* centers,
@@ -1668,6 +1645,22 @@ int rqsid_assign_x(const void* x, int32_t x_format, int64_t n_rows, int32_t dim,
   int rc = ensure_attrs();
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
+  const bool norm = res_normalize != 0;
+
+  AssignShape shape;
+  shape.x_format = x_format;
+  shape.n_rows = n_rows;
+  shape.dim = dim;
+  shape.n_segments = n_segments;
+  shape.cand_count_max = cand_count_max;
+  shape.res_levels = res_levels;
+  shape.norm = norm;
+  shape.screen_terms = screen_terms;
+  shape.has_cand_lid = cand_lid != nullptr;
+  shape.has_den_out = den_out != nullptr;
+  const AssignPlan plan = plan_assign(shape, read_assign_env());
+
+  const AssignWorkspace ws(n_rows, workspace);
   AssignParams p{};
   p.x = static_cast<const float*>(x);  // 16-bit formats: read as such by the x16 kernels only
   p.dim = dim;
@@ -1687,152 +1680,77 @@ int rqsid_assign_x(const void* x, int32_t x_format, int64_t n_rows, int32_t dim,
   p.seg_flags = seg_flags;
   p.out_local = out_local;
   p.out_global = out_global;
-  p.work_count = (int32_t*)workspace;
-  p.work = (WorkItem*)((char*)workspace + 256);
+  p.work_count = ws.header;
+  p.work = ws.work;
   p.work_cap = n_rows;
   p.work_idx = nullptr;
-  int32_t* tile_seg = (int32_t*)((char*)workspace + 256 + n_rows * (int64_t)sizeof(WorkItem));
-  int32_t* work_idx = tile_seg + (n_rows * 4 + 255) / 256 * 64;
   p.acc_rel = accumulation_rel(dim);
+  p.terms = plan.t3 ? 3 : 1;
   p.ca = ca;
   p.seg_ca = seg_ca;
   p.cb = cb;
   p.seg_cb = seg_cb;
   p.den_in = den_in;
   p.den_out = den_out;
-  const bool norm = res_normalize != 0;
   // header ints [0, 60) per call; [60, 64) hold the sticky error word (kErrSlot), zeroed by the allocator
   if (fill_async(workspace, 0, 4 * kErrSlot, st) != hipSuccess) return fail(RQSID_E_LAUNCH, "assign: memset");
-  const unsigned grid = (unsigned)((max_tiles + 7) / 8 * 8);  // XCD remap needs a multiple of 8
-  // Measured on MI355X (tools/screen_sweep.py): independent blocks per CU beat ring depth: NT4 with
-  // S=2 runs 3 blocks/CU, NT8 with S=2 runs 2 blocks/CU (RQSID_SCREEN_VARIANT=1/3 select the older
-  // deeper-ring single-block configurations for comparison).
-  // Terms: the 3-term screen (rounding residuals of both operands summed by two more MFMAs) shrinks
-  // the bound ~5x at 2 blocks/CU; auto picks it for residual levels with <= 128 candidates, where
-  // trained codebooks leave the most rows inside the 1-term bound ("Screen terms").
-  // (The 8-tile form has no 3-term build: its second accumulator set does not fit 256 VGPRs.)
-  // ONE: single-pass segments take the collapsed-bound epilogue (RQSID_SCREEN_VARIANT=2: the
-  // per-candidate two-sweep list epilogue, for comparison).
-  // Wider first-residual levels (the XL preset's middle level: 256 candidates per parent) take the
-  // 3-term screen in two 128-candidate passes: the 1-term bound leaves ~2/3 of those rows to the fp64
-  // re-score (measured: 4.1 M of 6.25 M rows, 14.3 ms).
-  const bool t3 = (cand_count_max <= 128 && (screen_terms == 3 || (screen_terms == 0 && res_levels >= 1))) ||
-                  (cand_count_max <= 256 && (screen_terms == 3 || (screen_terms == 0 && res_levels == 1)));
-  p.terms = t3 ? 3 : 1;
-  const bool legacy = screen_variant() == 2;
-  // the persistent streamed kernel (assign_stream.hip): 512-d rows, single-pass segments, no local-id
-  // remap, den_out present whenever it normalises a first-level residual
-  const int nt = t3 || cand_count_max <= 128 ? 4 : 8;
-  const bool stream_ok = dim == 512 && cand_count_max <= 256 && !cand_lid && (res_levels != 1 || !norm || den_out) &&
-                         n_rows >= 64 * 256 && (int64_t)n_segments + 1 <= n_rows &&
-                         stream_supported(nt, t3, res_levels, norm);
-  // Default (variant 0): the ping-pong form for 1-term 256-candidate RESIDUAL levels (gathered rows;
-  // measured L2 of the bench 7.58 vs 7.92 ms), the per-tile kernel elsewhere (L0 3.37 vs 3.99, L1 6.04 vs
-  // 6.54 ms; the XL preset's 256-candidate level 0 on contiguous rows 3.03 vs 3.62-3.65 ms).
-  // Variant 1 forces the per-tile kernel, variant 5 the stream forms (RQSID_STREAM_SHAPE).
-  const int variant = screen_variant();
-  const int shape = variant == 5 ? 0 : (variant == 0 && nt == 8 && !t3 && res_levels >= 1 ? 88 : -1);
-  // 16-bit rows (x16): the per-tile form only; the streamed, producer/consumer, row- and centre-resident screens
-  // and the candidate split are fp32-row kernels, and RQSID_SCREEN_VARIANT values that name them are ignored
-  const bool use_stream = !x16 && stream_ok && shape >= 0 && variant != 6;
-  // the centre-resident screen (assign_resident.hip): variant 6 forces it wherever it applies (1-term,
-  // <= 256 candidates).  Not the default yet: measured L2 of the bench 8.0-9.1 ms against the ping-pong
-  // form's 7.6 ms ('Centre-resident screen')
-  const bool res_ok = resident_supported(dim, cand_count_max, t3, res_levels) && (int64_t)n_segments + 1 <= n_rows &&
-                      (res_levels != 1 || !norm || den_out);
-  const bool use_res = !x16 && res_ok && variant == 6;
-  // the row-resident screen (assign_rows.hip): variant 8 forces it wherever it applies (1-term levels of
-  // 512-d rows with <= 512 candidates)
-  // default for 1-term residual levels wider than 256 candidates (the XL preset's 512-candidate last level:
-  // 7.0 vs 14.8 ms for the candidate-split screen, profiles/r4_xl_rows_ab.txt); the 256-candidate PROD level
-  // keeps the ping-pong form (7.4 vs 7.6-7.8 ms)
-  const bool use_rows = !x16 && (variant == 8 || (variant == 0 && res_levels >= 1 && cand_count_max > 256)) &&
-                        rows_supported(dim, cand_count_max, t3, res_levels, norm) && (int64_t)n_segments + 1 <= n_rows;
-  // the producer/consumer screen (assign_pc.hip): the default for the residual levels it covers (PROD level 1,
-  // 3-term <= 128 candidates, and level 2, 1-term <= 256); RQSID_PC=0 keeps the older
-  // dispatch above for A/B, variant 9 forces it wherever it applies
-  const char* pce = getenv("RQSID_PC");
-  const bool pc_ok = pc_supported(dim, cand_count_max, t3, res_levels) &&
-                     (res_levels != 1 || !norm || den_out) && (int64_t)n_segments + 1 <= n_rows &&
-                     pc_desc_bytes(n_rows, n_segments) <= resident_desc_bytes(n_rows);
-  // (default: the 1-term levels; RQSID_PC=2 takes the 3-term ones too, RQSID_PC=0 none)
-  const int pc_mode = pce ? atoi(pce) : 1;
-  const bool use_pc = !x16 && pc_ok && (variant == 9 || (variant == 0 && (pc_mode >= 2 || (pc_mode == 1 && !t3))));
-  if (use_pc) {
-    // R-row tile offsets in the compact-list area, the tile map in the tile_seg slot, the tile descriptors in
-    // the resident screen's descriptor area; a failed launch returns before the compaction and re-score
-    int4* desc = reinterpret_cast<int4*>(work_idx + (n_rows * 4 + 255) / 256 * 64);
-    if ((rc = launch_pc_screen(p, t3, res_levels, norm, tile_seg, work_idx, desc, n_rows, st))) return rc;
-    if ((rc = check_launch("assign_pc"))) return rc;
-    hipLaunchKernelGGL(sentinel_compact_kernel, dim3((unsigned)cdiv(n_rows, kCompactRows)), dim3(256), 0, st, out_global,
-                       n_rows, p.work_count, work_idx, n_rows);
-    p.work_idx = work_idx;
-  } else if (use_rows) {
-    // R-row tile offsets in the compact-list area, the tile map in the tile_seg slot; compact work list
-    if ((rc = launch_rows_screen(p, res_levels, norm, tile_seg, work_idx, n_rows, st))) return rc;
-  } else if (use_res) {
-    p.err = p.work_count + 48;  // zeroed with the workspace header above
-    const char* fc = getenv("RQSID_TEST_FORCE_SPIN_CAP");
-    p.force_cap = fc && atoi(fc) ? 1 : 0;
-    int4* desc = reinterpret_cast<int4*>(work_idx + (n_rows * 4 + 255) / 256 * 64);
-    // tile_seg's slot holds the segment of each ambiguous row
-    if ((rc = launch_resident_screen(p, t3, res_levels, norm, desc, work_idx, tile_seg, n_rows, st))) return rc;
-    // re-score rows carry the sentinel -2 and their pass masks at work[row] (the 32-row tile offsets in
-    // the compact-list area are dead by now); the expand pass makes them work items
-    hipLaunchKernelGGL(sentinel_compact_kernel, dim3((unsigned)cdiv(n_rows, kCompactRows)), dim3(256), 0, st, out_global,
-                       n_rows, p.work_count, work_idx, n_rows);
-    p.work_idx = work_idx;
-    launch_resident_expand(p, tile_seg, t3, n_rows, st);
-  } else if (use_stream) {
-    // the 256-row tile offsets live in the compact-list area until the compaction pass
-    // a failed stream launch returns its status here: the compaction and re-score below must never run
-    // over an out_global the screen did not write
-    if ((rc = launch_stream_screen(p, nt, t3, res_levels, norm, tile_seg, work_idx, n_rows, shape, st))) return rc;
-    if ((rc = check_launch("assign_stream"))) return rc;
-    hipLaunchKernelGGL(sentinel_compact_kernel, dim3((unsigned)cdiv(n_rows, kCompactRows)), dim3(256), 0, st, out_global,
-                       n_rows, p.work_count, work_idx, n_rows);
-    p.work_idx = work_idx;
-  } else {
-    if (n_segments > 1) {  // (tiles <= rows: the map fits its workspace slot)
-      hipLaunchKernelGGL(tile_seg128_kernel, dim3(grid_cap(cdiv(max_tiles, 256), 4096)), dim3(256), 0, st, seg_tile_off,
-                         n_segments, n_rows, tile_seg);
-      p.tile_seg = tile_seg;
-    }
+
+  // a failed persistent launch returns its status here: the compaction and re-score below must never run over
+  // an out_global the screen did not write
+  switch (plan.screen) {
+    case AssignPlan::kPc:
+      if ((rc = launch_pc_screen(p, plan, res_levels, norm, ws, n_rows, st))) return rc;
+      if ((rc = check_launch("assign_pc"))) return rc;
+      break;
+    case AssignPlan::kRows:
+      if ((rc = launch_rows_screen(p, plan, res_levels, norm, ws, n_rows, st))) return rc;
+      break;
+    case AssignPlan::kResident:
+      p.err = ws.header + 48;  // zeroed with the workspace header above
+      p.force_cap = plan.force_cap ? 1 : 0;
+      if ((rc = launch_resident_screen(p, res_levels, norm, ws, n_rows, st))) return rc;
+      break;
+    case AssignPlan::kStream:
+      if ((rc = launch_stream_screen(p, plan, res_levels, norm, ws, n_rows, st))) return rc;
+      if ((rc = check_launch("assign_stream"))) return rc;
+      break;
+    case AssignPlan::kTile:
+      if (n_segments > 1) {  // (tiles <= rows: the map fits its workspace slot)
+        hipLaunchKernelGGL(tile_seg128_kernel, dim3(grid_cap(cdiv(max_tiles, 256), 4096)), dim3(256), 0, st, seg_tile_off,
+                           n_segments, n_rows, ws.tile_seg);
+        p.tile_seg = ws.tile_seg;
+      }
+      dispatch_xf(x_format, [&](auto XF) {  // (grid: the XCD remap needs a multiple of 8)
+        launch_tile_screen<XF()>(p, plan, res_levels, norm, (unsigned)((max_tiles + 7) / 8 * 8), st);
+      });
+      break;
   }
-  // candidate-split single pass (CW = 2) for segments wider than one wave's tiles: 3-term <= 256
-  // candidates, 1-term <= 512 (the XL preset's middle and last levels); RQSID_SCREEN_VARIANT=7 (or 2)
-  // keeps the multi-pass screen for comparison
-  const bool split = !legacy && variant != 7 && dim <= kSplitDim;
-  if (use_pc || use_stream || use_res || use_rows) {
-  } else if (x_format == RQSID_X_F16) launch_screen_x16<RQSID_X_F16>(p, res_levels, norm, grid, t3, cand_count_max, legacy, st);
-  else if (x_format == RQSID_X_BF16) launch_screen_x16<RQSID_X_BF16>(p, res_levels, norm, grid, t3, cand_count_max, legacy, st);
-  else if (t3 && cand_count_max > 128 && split) launch_screen<4, kSplitS, true, true, 2>(p, res_levels, norm, grid, st);
-  else if (t3) launch_screen2<4, 2, true>(p, res_levels, norm, grid, !legacy && cand_count_max <= 128, st);
-  else if (cand_count_max <= 128) launch_screen2<4, 2, false>(p, res_levels, norm, grid, !legacy, st);
-  else if (cand_count_max <= 256) launch_screen2<8, 2, false>(p, res_levels, norm, grid, !legacy, st);
-  else if (cand_count_max <= 512 && split) launch_screen<8, kSplitS, false, true, 2>(p, res_levels, norm, grid, st);
-  else launch_screen<8, 2, false, false>(p, res_levels, norm, grid, st);
+  if (plan.compact) {  // rows the screen left to the re-score carry the sentinel -2 in out_global
+    hipLaunchKernelGGL(sentinel_compact_kernel, dim3((unsigned)cdiv(n_rows, kCompactRows)), dim3(256), 0, st, out_global,
+                       n_rows, p.work_count, ws.work_idx, n_rows);
+    p.work_idx = ws.work_idx;
+  }
+  // resident screen: the listed rows' pass masks at work[row] become work items
+  if (plan.expand) launch_resident_expand(p, ws.tile_seg, n_rows, st);
   if ((rc = check_launch("assign_screen"))) return rc;
-  // two rows per wave for rows of <= 512 dims (RQSID_RESCORE_FULL=1: one row per wave, for A/B)
-  const char* ef = getenv("RQSID_RESCORE_FULL");
-  const bool half = dim <= kHalfDim && !(ef && atoi(ef));
-  // rows the screen left with "every candidate" get an fp32 list first (RQSID_NO_RESCREEN=1: off, A/B)
-  const char* nr = getenv("RQSID_NO_RESCREEN");
-  int32_t* ovf_list = nullptr;
-  if (dim <= kHalfDim && !(nr && atoi(nr)) && cand_count_max > kMaxList) {
-    ovf_list = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(work_idx) + (n_rows * 4 + 255) / 256 * 256 +
-                                          resident_desc_bytes(n_rows));
-    hipLaunchKernelGGL(overflow_list_kernel, dim3(grid_cap(cdiv(n_rows, 256), 1024)), dim3(256), 0, st, p, ovf_list);
-    if (x_format == RQSID_X_F16) launch_rescreen_xf<RQSID_X_F16>(p, res_levels, norm, ovf_list, st);
-    else if (x_format == RQSID_X_BF16) launch_rescreen_xf<RQSID_X_BF16>(p, res_levels, norm, ovf_list, st);
-    else launch_rescreen_xf<RQSID_X_F32>(p, res_levels, norm, ovf_list, st);
+  const int32_t* ovf_list = nullptr;
+  if (plan.rescreen) {  // rows the screen left with "every candidate" get an fp32 list first
+    ovf_list = ws.ovf_list;
+    hipLaunchKernelGGL(overflow_list_kernel, dim3(grid_cap(cdiv(n_rows, 256), 1024)), dim3(256), 0, st, p, ws.ovf_list);
+    dispatch_xf(x_format, [&](auto XF) {
+      constexpr int xf = decltype(XF)::value;
+      dispatch_rl_norm(res_levels, norm,
+                       [&](auto RL, auto NORM) { launch_rescreen<xf, RL(), NORM()>(p, ovf_list, st); });
+    });
     if ((rc = check_launch("assign_rescreen"))) return rc;
   }
-  if (x_format == RQSID_X_F16) launch_exact_xf<RQSID_X_F16>(p, res_levels, norm, ovf_list, half, st);
-  else if (x_format == RQSID_X_BF16) launch_exact_xf<RQSID_X_BF16>(p, res_levels, norm, ovf_list, half, st);
-  else launch_exact_xf<RQSID_X_F32>(p, res_levels, norm, ovf_list, half, st);
+  dispatch_xf(x_format, [&](auto XF) {
+    constexpr int xf = decltype(XF)::value;
+    dispatch_rl_norm(res_levels, norm,
+                     [&](auto RL, auto NORM) { launch_exact<xf, RL(), NORM()>(p, ovf_list, plan.half, st); });
+  });
   if ((rc = check_launch("assign_rescore"))) return rc;
-  if (use_res) {
+  if (plan.read_err_word) {
     // the resident screen's role waits are capped (assign_resident.hip): a wave that gave up waiting
     // left wrong IDs behind, so the call fails instead of returning them (one readback, opt-in path)
     int32_t err = 0;

@@ -1,9 +1,13 @@
-// assign_common.h — definitions shared by the screening kernels (assign.hip: per-tile kernel for any
-// shape; assign_stream.hip: the persistent streamed kernel for single-pass segments).  Not ABI.
+// assign_common.h — definitions shared by the five translation units of rqsid_assign: assign.hip (the entry
+// point, the per-tile screen for any shape, the re-screen and the exact re-score) and the persistent screens
+// assign_stream.hip (streamed / ping-pong), assign_rows.hip (row-resident), assign_resident.hip
+// (centre-resident) and assign_pc.hip (producer/consumer).  Which one runs: assign_plan.h.  Not ABI.
 #pragma once
 #include <cmath>
 #include <cstdlib>
+#include <type_traits>
 
+#include "assign_plan.h"
 #include "internal.h"
 
 #ifndef RQSID_AB_MODE  // A/B timing builds only (tools/ab_build.sh): 1 no epilogue, 2 + no MFMA, 3 DMA only
@@ -43,7 +47,7 @@ struct WorkItem {
   int32_t pad;
   uint16_t cand[kMaxList];
 };
-static_assert(sizeof(WorkItem) == 32, "work item layout");
+static_assert(sizeof(WorkItem) == kPlanWorkItemBytes && kMaxList == kPlanMaxList, "assign_plan.h constants");
 
 struct AssignParams {
   const float* x;
@@ -544,34 +548,87 @@ __device__ __forceinline__ void row_frag(const float4 xa, const float4 xc, const
 }
 
 
-// table-wide epilogue constants written by rqsid_prepare_centers into meta row k:
-// {2^-s, max |ec2|/|c|, max |ec1|/|c|, max |c|} (rounded up)
-// shape: 88 ping-pong 8-wave form, 83 / 42 streamed 8x3 / 4x2 forms, 0 = RQSID_STREAM_SHAPE (default 83)
-int launch_stream_screen(const AssignParams& p, int nt, bool t3, int rl, bool norm, int32_t* tile_seg,
-                         int32_t* seg_tile256, int64_t cap, int shape, hipStream_t st);
-bool stream_supported(int nt, bool t3, int rl, bool norm);
-// R-row tiling of the segments on the device: seg_tiles[s] (n_segments + 1 ints) and tile -> segment
-// (tile_seg, cap / R + n_segments entries at most)
-void launch_tiling(const AssignParams& p, int R, int32_t* tile_seg, int32_t* seg_tiles, int64_t cap, hipStream_t st);
-// row-resident screen (assign_rows.hip): 512-d rows, 1 term, <= 512 candidates per segment
-bool rows_supported(int dim, int cand_count_max, bool t3, int rl, bool norm);
-int launch_rows_screen(const AssignParams& p, int rl, bool norm, int32_t* tile_seg, int32_t* seg_tiles, int64_t cap,
-                       hipStream_t st);
+// ---------------------------------------------------------------------------
+// host side: workspace pointers, template ladders, the persistent launch
+// ---------------------------------------------------------------------------
+// the areas of AssignWorkspaceMap (assign_plan.h: offsets, and which screen keeps what where) as pointers
+struct AssignWorkspace {
+  int32_t* header;
+  WorkItem* work;
+  int32_t* tile_seg;
+  int32_t* work_idx;
+  void* desc;
+  int32_t* ovf_list;
+  int64_t total_bytes;
+  AssignWorkspace(int64_t n_rows, void* base) {
+    const AssignWorkspaceMap m(n_rows);
+    char* b = static_cast<char*>(base);
+    header = reinterpret_cast<int32_t*>(b + m.header);
+    work = reinterpret_cast<WorkItem*>(b + m.work);
+    tile_seg = reinterpret_cast<int32_t*>(b + m.tile_seg);
+    work_idx = reinterpret_cast<int32_t*>(b + m.work_idx);
+    desc = b + m.desc;
+    ovf_list = reinterpret_cast<int32_t*>(b + m.ovf_list);
+    total_bytes = m.total_bytes;
+  }
+};
+static_assert(sizeof(int4) == kPlanDescBytesPerRow, "assign_plan.h constants");
 
-// producer/consumer screen (assign_pc.hip): 512-d residual levels, 3-term <= 128 or 1-term <= 256 candidates
-// per segment; desc_mem: pc_desc_bytes(n_rows, n_segments) of workspace; seg_tiles: n_segments + 1 ints
-bool pc_supported(int dim, int cand_count_max, bool t3, int rl);
-int64_t pc_desc_bytes(int64_t n_rows, int32_t n_segments);
-int launch_pc_screen(const AssignParams& p, bool t3, int rl, bool norm, int32_t* tile_seg, int32_t* seg_tiles,
-                     void* desc_mem, int64_t cap, hipStream_t st);
+// f(integral_constant<int, RL>, bool_constant<NORM>) for the five builds of the residual chain; a screen
+// without one of them refuses it inside f (if constexpr), so nothing more is instantiated than f names
+template <typename F>
+auto dispatch_rl_norm(int rl, bool norm, F&& f) {
+  using std::integral_constant;
+  if (rl == 0) return f(integral_constant<int, 0>{}, std::false_type{});
+  if (rl == 1) return norm ? f(integral_constant<int, 1>{}, std::true_type{}) : f(integral_constant<int, 1>{}, std::false_type{});
+  return norm ? f(integral_constant<int, 2>{}, std::true_type{}) : f(integral_constant<int, 2>{}, std::false_type{});
+}
+// f(integral_constant<int, XF>) for the three row formats (RQSID_X_*)
+template <typename F>
+auto dispatch_xf(int x_format, F&& f) {
+  using std::integral_constant;
+  if (x_format == RQSID_X_F16) return f(integral_constant<int, RQSID_X_F16>{});
+  if (x_format == RQSID_X_BF16) return f(integral_constant<int, RQSID_X_BF16>{});
+  return f(integral_constant<int, RQSID_X_F32>{});
+}
 
-// centre-resident screen (assign_resident.hip): 512-d rows, <= 256 candidates per segment (1 term) or
-// <= 128 (3 terms).  desc: resident_desc_bytes(n_rows) of workspace; seg_tile32: n_segments + 1 ints.
-bool resident_supported(int dim, int cand_count_max, bool t3, int rl);
-int64_t resident_desc_bytes(int64_t n_rows);
-int launch_resident_screen(const AssignParams& p, bool t3, int rl, bool norm, int4* desc, int32_t* seg_tile32,
-                           int32_t* seg_of_row, int64_t cap, hipStream_t st);
+// Launch of a persistent screen: the kernel's dynamic-LDS limit is raised once per device (the flag is per
+// Kernel), the grid is every block resident at once, ncu * blocks_per_cu, clipped to max_tiles (kNoClip: not
+// clipped) and rounded down to a multiple of 8 (XCD-contiguous tile runs), 8 at least.  false: device query
+// or attribute failure, nothing launched.
+constexpr int64_t kNoClip = INT64_MAX;
+template <auto Kernel, typename... Args>
+bool launch_persistent(int lds_bytes, int threads, int blocks_per_cu, int64_t max_tiles, hipStream_t st, Args... args) {
+  static bool attr[kMaxDevices] = {};
+  const int dev = current_device(), ncu = device_cu_count();
+  if (dev < 0 || !ncu) return false;
+  if (!attr[dev]) {
+    if (hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes) != hipSuccess)
+      return false;
+    attr[dev] = true;
+  }
+  int64_t g = (int64_t)ncu * blocks_per_cu;
+  if (g > max_tiles) g = max_tiles;
+  g = g / 8 * 8;
+  if (g < 8) g = 8;
+  hipLaunchKernelGGL(Kernel, dim3((unsigned)g), dim3(threads), lds_bytes, st, args...);
+  return true;
+}
+
+// The screens' entry points.  Each takes its form from the plan (assign_plan.h) and its areas from the
+// workspace; cap = n_rows, the capacity of every per-row area.  0 or the failed call's status.
+int launch_stream_screen(const AssignParams& p, const AssignPlan& plan, int rl, bool norm, const AssignWorkspace& ws,
+                         int64_t cap, hipStream_t st);
+int launch_rows_screen(const AssignParams& p, const AssignPlan& plan, int rl, bool norm, const AssignWorkspace& ws,
+                       int64_t cap, hipStream_t st);
+int launch_pc_screen(const AssignParams& p, const AssignPlan& plan, int rl, bool norm, const AssignWorkspace& ws,
+                     int64_t cap, hipStream_t st);
+int launch_resident_screen(const AssignParams& p, int rl, bool norm, const AssignWorkspace& ws, int64_t cap,
+                           hipStream_t st);
 // after the sentinel compaction: pass masks of the listed rows -> work items (p.work_idx set)
-void launch_resident_expand(const AssignParams& p, const int32_t* seg_of_row, bool t3, int64_t n_rows, hipStream_t st);
+void launch_resident_expand(const AssignParams& p, const int32_t* seg_of_row, int64_t n_rows, hipStream_t st);
+// R-row tiling of the segments on the device: seg_tiles[s] (n_segments + 1 ints) and tile -> segment
+// (tile_seg, cap / R + n_segments entries at most, which is also the returned bound on the tile count)
+int64_t launch_tiling(const AssignParams& p, int R, int32_t* tile_seg, int32_t* seg_tiles, int64_t cap, hipStream_t st);
 
 }  // namespace rqsid

@@ -7,16 +7,18 @@
 // ONE = true): fp16 MFMA screen, the collapsed per-candidate bound, pass-bit masks, fp64 re-score of the
 // rows the bound leaves ambiguous; the returned IDs are the exact argmin, bit-identical to every other form.
 // What differs is who does what:
-//  * One persistent 512-thread block per CU, 128-row tiles of one segment, XCD-contiguous tile runs.
+//  * One persistent 768-thread block per CU (12 waves, three per SIMD), 128-row tiles of one segment,
+//    XCD-contiguous tile runs.
 //  * Waves 0-3 are CONSUMERS (one per SIMD): each owns 32 rows of the tile and runs only LDS fragment
 //    reads, MFMAs (32 rows x all candidates, 128 accumulator registers) and the tile's bound epilogue and
 //    output stores.  They issue no global load, so no wave that computes ever stalls on DMA issue.
-//  * Waves 4-7 are PRODUCERS (one per SIMD, beside a consumer): they issue every global_load_lds of the
-//    block (row chunks from HBM four chunks ahead, the candidates' fp16 centre chunks two ahead, the next
-//    tile's header in two dependent levels), run the fused residual chain on the landed fp32 rows and
+//  * Waves 4-7 are ROW PRODUCERS (one per SIMD, beside a consumer): they issue the row chunks'
+//    global_load_lds (from HBM, four chunks ahead), run the fused residual chain on the landed fp32 rows and
 //    write the MFMA B operand (fp16 rows, and their rounding residuals for the 3-term screen) into a
 //    double-buffered LDS image, and reduce the rows' bound coefficients {m2, A2} once per tile.  So the
 //    residual chain's VALU of one wave runs beside the MFMAs of the other wave on the same SIMD.
+//  * Waves 8-11 are LOADERS (one per SIMD): the candidates' fp16 centre chunks two ahead and the next
+//    tile's header in two dependent levels.
 //  * One barrier per 32-dim chunk; every producer wait is a counted vmcnt whose count depends only on the
 //    chunk's position in the tile (a fixed number of DMA ops per phase, dummy sources when a tile has no
 //    successor), and the block waits vmcnt(0) before it exits.
@@ -52,6 +54,7 @@ struct PcDesc {
   int32_t s, t0, nrows, cnt, cbase, flags, ca_row, cb_row;  // flags: bit 0 no screen (penalty / no candidates), bit 1 penalty
 };
 static_assert(sizeof(PcDesc) == 32, "descriptor layout");
+static_assert(kQDim == kPlanPcDim && kQRows == kPlanPcRows && sizeof(PcDesc) == kPlanPcDescBytes, "assign_plan.h constants");
 
 template <int NT, int RL, bool T3>
 struct PcLayout {
@@ -1070,83 +1073,30 @@ __global__ __launch_bounds__(768, 3) void assign_pcw_kernel(AssignParams p, cons
 #endif
 }
 
-template <int RL, bool NORM>
-bool launch_pcw(const AssignParams& p, const int32_t* seg_tiles, const PcDesc* desc, int64_t max_tiles, hipStream_t st) {
-  using L = PcwLayout<RL>;
-  static bool attr[kMaxDevices] = {};
-  const int dev = current_device(), ncu = device_cu_count();
-  if (dev < 0 || !ncu) return false;
-  if (!attr[dev]) {
-    if (hipFuncSetAttribute((const void*)assign_pcw_kernel<RL, NORM>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            L::kBytes) != hipSuccess)
-      return false;
-    attr[dev] = true;
-  }
-  int64_t g = ncu;  // one persistent block per CU
-  if (g > max_tiles) g = max_tiles;
-  g = g / 8 * 8;
-  if (g < 8) g = 8;
-  hipLaunchKernelGGL((assign_pcw_kernel<RL, NORM>), dim3((unsigned)g), dim3(768), L::kBytes, st, p, seg_tiles, desc);
-  return true;
-}
-
-template <int NT, int RL, bool NORM, bool T3>
-bool launch_pc(const AssignParams& p, const int32_t* seg_tiles, const PcDesc* desc, int64_t max_tiles, hipStream_t st) {
-  using L = PcLayout<NT, RL, T3>;
-  static bool attr[kMaxDevices] = {};
-  const int dev = current_device(), ncu = device_cu_count();
-  if (dev < 0 || !ncu) return false;
-  if (!attr[dev]) {
-    if (hipFuncSetAttribute((const void*)assign_pc_kernel<NT, RL, NORM, T3>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            L::kBytes) != hipSuccess)
-      return false;
-    attr[dev] = true;
-  }
-  int64_t g = ncu;  // one persistent block per CU
-  if (g > max_tiles) g = max_tiles;
-  g = g / 8 * 8;
-  if (g < 8) g = 8;
-  hipLaunchKernelGGL((assign_pc_kernel<NT, RL, NORM, T3>), dim3((unsigned)g), dim3(768), L::kBytes, st, p, seg_tiles, desc);
-  return true;
-}
-
 }  // namespace
 
-bool pc_supported(int dim, int cand_count_max, bool t3, int rl) {
-  if (dim != kQDim || rl < 1 || rl > 2) return false;
-  return t3 ? cand_count_max <= 128 : cand_count_max <= 256;
-}
-
-int64_t pc_desc_bytes(int64_t n_rows, int32_t n_segments) {
-  return ((n_rows > 0 ? n_rows : 0) / kQRows + (int64_t)n_segments + 1) * (int64_t)sizeof(PcDesc);
-}
-
-int launch_pc_screen(const AssignParams& p, bool t3, int rl, bool norm, int32_t* tile_seg, int32_t* seg_tiles,
-                     void* desc_mem, int64_t cap, hipStream_t st) {
-  PcDesc* desc = reinterpret_cast<PcDesc*>(desc_mem);
-  // RQSID_PCW=1: the wide form (256-row tiles) on 1-term levels, an A/B only -- measured slower
-  const char* we = getenv("RQSID_PCW");
-  const bool wide = !t3 && we && atoi(we) == 1;
-  const int R = wide ? kWRows : kQRows;
-  launch_tiling(p, R, tile_seg, seg_tiles, cap, st);
-  const int64_t max_tiles = cap / R + p.n_segments;
+// R-row tile offsets in the compact-list area, the tile map in the tile_seg slot, the tile descriptors in the
+// descriptor area (plan_assign checked that they fit); one persistent 768-thread block per CU
+int launch_pc_screen(const AssignParams& p, const AssignPlan& plan, int rl, bool norm, const AssignWorkspace& ws,
+                     int64_t cap, hipStream_t st) {
+  PcDesc* desc = static_cast<PcDesc*>(ws.desc);
+  const int32_t* seg_tiles = ws.work_idx;
+  const int R = plan.pc_wide ? kWRows : kQRows;
+  const int64_t max_tiles = launch_tiling(p, R, ws.tile_seg, ws.work_idx, cap, st);
   hipLaunchKernelGGL(pc_desc_kernel, dim3(grid_cap(cdiv(max_tiles, 256), 4096)), dim3(256), 0, st, p, seg_tiles,
                      max_tiles, R, desc);
-  bool ok = false;
-  if (wide) {
-    if (rl == 1) ok = norm ? launch_pcw<1, true>(p, seg_tiles, desc, max_tiles, st) : launch_pcw<1, false>(p, seg_tiles, desc, max_tiles, st);
-    else ok = norm ? launch_pcw<2, true>(p, seg_tiles, desc, max_tiles, st) : launch_pcw<2, false>(p, seg_tiles, desc, max_tiles, st);
-  } else if (t3) {
-    if (rl == 1) ok = norm ? launch_pc<4, 1, true, true>(p, seg_tiles, desc, max_tiles, st)
-                           : launch_pc<4, 1, false, true>(p, seg_tiles, desc, max_tiles, st);
-    else ok = norm ? launch_pc<4, 2, true, true>(p, seg_tiles, desc, max_tiles, st)
-                   : launch_pc<4, 2, false, true>(p, seg_tiles, desc, max_tiles, st);
-  } else {
-    if (rl == 1) ok = norm ? launch_pc<8, 1, true, false>(p, seg_tiles, desc, max_tiles, st)
-                           : launch_pc<8, 1, false, false>(p, seg_tiles, desc, max_tiles, st);
-    else ok = norm ? launch_pc<8, 2, true, false>(p, seg_tiles, desc, max_tiles, st)
-                   : launch_pc<8, 2, false, false>(p, seg_tiles, desc, max_tiles, st);
-  }
+  const bool ok = dispatch_rl_norm(rl, norm, [&](auto RL, auto NORM) {
+    if constexpr (RL() == 0) return false;  // residual levels only (pc_supported)
+    else if (plan.pc_wide)
+      return launch_persistent<assign_pcw_kernel<RL(), NORM()>>(PcwLayout<RL()>::kBytes, 768, 1, max_tiles, st, p, seg_tiles,
+                                                                desc);
+    else if (plan.t3)
+      return launch_persistent<assign_pc_kernel<4, RL(), NORM(), true>>(PcLayout<4, RL(), true>::kBytes, 768, 1, max_tiles,
+                                                                        st, p, seg_tiles, desc);
+    else
+      return launch_persistent<assign_pc_kernel<8, RL(), NORM(), false>>(PcLayout<8, RL(), false>::kBytes, 768, 1, max_tiles,
+                                                                         st, p, seg_tiles, desc);
+  });
   return ok ? RQSID_OK : fail(RQSID_E_LAUNCH, "assign: producer/consumer screen launch failed (device query / LDS attribute)");
 }
 

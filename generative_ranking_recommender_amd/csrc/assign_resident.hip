@@ -46,6 +46,7 @@ namespace {
 #define RQ_PF 2  // fragment prefetch distance (k-steps)
 #endif
 constexpr int kRD = 512;                 // row width of this kernel
+static_assert(kRD == kPlanResDim, "assign_plan.h constants");
 constexpr int kRT = 32;                  // rows per tile (the MFMA's N)
 constexpr int kKS = kRD / 16;            // k-steps of v_mfma_f32_32x32x16_f16
 constexpr int kGS = (kRT + 1) * 16;      // bytes per eight-dim group: 32 rows x 16 B + 16 B pad
@@ -900,35 +901,6 @@ __global__ __launch_bounds__(256) void res_desc_kernel(const int32_t* __restrict
   }
 }
 
-struct DevState {
-  int ncu = 0;
-  bool attr[3][2] = {};  // [RL][NORM]
-};
-DevState g_dev[64];
-
-template <int RL, bool NORM>
-int launch_res(const AssignParams& p, const int4* desc, const int32_t* seg_tile32, int32_t* seg_of_row, hipStream_t st) {
-  using L = ResLayout<RL>;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return fail(RQSID_E_LAUNCH, "assign: hipGetDevice");
-  DevState& ds = g_dev[dev];
-  if (!ds.ncu) {
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, dev) != hipSuccess) return fail(RQSID_E_LAUNCH, "assign: device properties");
-    ds.ncu = prop.multiProcessorCount;
-  }
-  const void* k = (const void*)assign_resident_kernel<RL, NORM>;
-  if (!ds.attr[RL][NORM]) {
-    if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, L::kBytes) != hipSuccess)
-      return fail(RQSID_E_LAUNCH, "assign: cannot raise the dynamic LDS limit (resident screen)");
-    ds.attr[RL][NORM] = true;
-  }
-  const unsigned g = (unsigned)(ds.ncu >= 8 ? ds.ncu / 8 * 8 : 8);  // one persistent block per CU
-  hipLaunchKernelGGL((assign_resident_kernel<RL, NORM>), dim3(g), dim3(kThreads), L::kBytes, st, p, desc, seg_tile32,
-                     seg_of_row);
-  return check_launch("assign_resident");
-}
-
 // Ambiguous rows of the resident screen -> work items for assign_rescore_kernel (after the sentinel
 // compaction listed them): work[row] holds one pass-mask word per candidate wave (bit j of word q =
 // list position 32 q + j); seg_of_row[row] the segment (~segment for a penalty / empty segment).
@@ -976,35 +948,28 @@ __global__ __launch_bounds__(256) void res_expand_kernel(AssignParams p, const i
 
 }  // namespace
 
-void launch_resident_expand(const AssignParams& p, const int32_t* seg_of_row, bool t3, int64_t n_rows, hipStream_t st) {
-  hipLaunchKernelGGL(res_expand_kernel, dim3(grid_cap(cdiv(n_rows, 256), 2048)), dim3(256), 0, st, p, seg_of_row,
-                     t3 ? 0 : kCW);
+void launch_resident_expand(const AssignParams& p, const int32_t* seg_of_row, int64_t n_rows, hipStream_t st) {
+  hipLaunchKernelGGL(res_expand_kernel, dim3(grid_cap(cdiv(n_rows, 256), 2048)), dim3(256), 0, st, p, seg_of_row, kCW);
 }
 
-bool resident_supported(int dim, int cand_count_max, bool t3, int rl) {
-  // one fp16 term only: the 3-term form (hi / lo centre waves) does not fit the LDS budget and
-  // registers beside the one-exchange epilogue (the per-tile screen serves those levels)
-  (void)rl;
-  return dim == kRD && cand_count_max >= 1 && cand_count_max <= 256 && !t3;
-}
-
-int64_t resident_desc_bytes(int64_t n_rows) { return (n_rows > 0 ? n_rows : 0) * (int64_t)sizeof(int4); }
-
-int launch_resident_screen(const AssignParams& p, bool t3, int rl, bool norm, int4* desc, int32_t* seg_tile32,
-                           int32_t* seg_of_row, int64_t cap, hipStream_t st) {
+// the 32-row tile offsets in the compact-list area, the tile descriptors in the descriptor area, the segment of
+// each ambiguous row in the tile_seg slot; one persistent block per CU
+int launch_resident_screen(const AssignParams& p, int rl, bool norm, const AssignWorkspace& ws, int64_t cap,
+                           hipStream_t st) {
+  int4* desc = static_cast<int4*>(ws.desc);
+  int32_t* seg_tile32 = ws.work_idx;
   hipLaunchKernelGGL(res_tiles_kernel, dim3(1), dim3(1024), 0, st, p.seg_row_off, p.n_segments, cap,
                      p.work_count ? p.work_count + kErrSlot : (int32_t*)nullptr, seg_tile32);
   hipLaunchKernelGGL(res_desc_kernel, dim3(grid_cap(cdiv(cap, 256), 4096)), dim3(256), 0, st, p.seg_row_off, seg_tile32,
                      p.n_segments, cap, desc);
   int rc = check_launch("assign_resident tiles");
   if (rc) return rc;
-#define RQ_R(RL, NORM, T3) return launch_res<RL, NORM>(p, desc, seg_tile32, seg_of_row, st)
-  if (t3) return fail(RQSID_E_ARG, "assign: the resident screen has no 3-term form");
-  if (rl == 0) RQ_R(0, false, false);
-  if (rl == 1) { if (norm) RQ_R(1, true, false); RQ_R(1, false, false); }
-  if (norm) RQ_R(2, true, false);
-  RQ_R(2, false, false);
-#undef RQ_R
+  const bool ok = dispatch_rl_norm(rl, norm, [&](auto RL, auto NORM) {
+    return launch_persistent<assign_resident_kernel<RL(), NORM()>>(ResLayout<RL()>::kBytes, kThreads, 1, kNoClip, st, p,
+                                                                   (const int4*)desc, (const int32_t*)seg_tile32, ws.tile_seg);
+  });
+  return ok ? check_launch("assign_resident")
+            : fail(RQSID_E_LAUNCH, "assign: resident screen launch failed (device query / LDS attribute)");
 }
 
 }  // namespace rqsid

@@ -25,6 +25,7 @@ namespace {
 constexpr int kRDim = 512;        // row width of this screen
 constexpr int kRNch = kRDim / 32; // 32-dim chunks
 constexpr int kRMaxCand = 512;    // candidates per segment
+static_assert(kRDim == kPlanRowsDim && kRMaxCand == kPlanRowsMaxCand, "assign_plan.h constants");
 #ifndef RQSID_ROWS_NTB
 #define RQSID_ROWS_NTB 2
 #endif
@@ -393,57 +394,30 @@ __global__ __launch_bounds__(W * 64, 2) void assign_rows_kernel(AssignParams p, 
   }
 }
 
-template <int W, int S, int SR, int NTB, int RL, bool NORM>
-bool launch_rows_one(const AssignParams& p, const int32_t* tile_seg, const int32_t* seg_tiles, hipStream_t st) {
-  using L = RowsLayout<W, S, SR, NTB>;
-  static bool attr[kMaxDevices] = {};
-  const int dev = current_device(), ncu = device_cu_count();
-  if (dev < 0 || !ncu) return false;
-  if (!attr[dev]) {
-    if (hipFuncSetAttribute((const void*)assign_rows_kernel<W, S, SR, NTB, RL, NORM>,
-                            hipFuncAttributeMaxDynamicSharedMemorySize, L::kBytes) != hipSuccess)
-      return false;
-    attr[dev] = true;
-  }
-  const int64_t g = (int64_t)ncu * L::kBlocks / 8 * 8;  // persistent: every block resident at once
-  hipLaunchKernelGGL((assign_rows_kernel<W, S, SR, NTB, RL, NORM>), dim3((unsigned)(g < 8 ? 8 : g)), dim3(W * 64),
-                     L::kBytes, st, p, tile_seg, seg_tiles);
-  return true;
-}
-
-// block shape RQSID_ROWS_SHAPE = 100 W + 10 S + SR (waves, centre ring stages, per-wave row ring stages):
-// 443 (the default) and 482: 4 waves, two blocks per CU (one block's row stream overlaps the other's
-// MFMAs); 883: 8 waves, one block per CU (half the centre bytes per row, the row stream exposed)
-int rows_shape() {
-  const char* e = getenv("RQSID_ROWS_SHAPE");
-  const int v = e ? atoi(e) : 443;
-  return v == 482 || v == 883 ? v : 443;
-}
-
+// block shape <W waves, S centre ring stages, SR per-wave row ring stages> (AssignEnv::rows_shape); persistent,
+// every block resident at once, the grid not clipped to the tile count
 template <int W, int S, int SR>
 bool launch_rows_w(const AssignParams& p, int rl, bool norm, const int32_t* tile_seg, const int32_t* seg_tiles,
                    hipStream_t st) {
-  if (rl == 0) return launch_rows_one<W, S, SR, kNTB, 0, false>(p, tile_seg, seg_tiles, st);
-  if (rl == 1) return !norm && launch_rows_one<W, S, SR, kNTB, 1, false>(p, tile_seg, seg_tiles, st);
-  if (norm) return launch_rows_one<W, S, SR, kNTB, 2, true>(p, tile_seg, seg_tiles, st);
-  return launch_rows_one<W, S, SR, kNTB, 2, false>(p, tile_seg, seg_tiles, st);
+  using L = RowsLayout<W, S, SR, kNTB>;
+  return dispatch_rl_norm(rl, norm, [&](auto RL, auto NORM) {
+    if constexpr (RL() == 1 && NORM()) return false;  // no such build (rows_supported)
+    else
+      return launch_persistent<assign_rows_kernel<W, S, SR, kNTB, RL(), NORM()>>(L::kBytes, W * 64, L::kBlocks, kNoClip, st,
+                                                                                 p, tile_seg, seg_tiles);
+  });
 }
 
 }  // namespace
 
-bool rows_supported(int dim, int cand_count_max, bool t3, int rl, bool norm) {
-  return dim == kRDim && !t3 && cand_count_max > 0 && cand_count_max <= kRMaxCand && rl >= 0 && rl <= 2 &&
-         !(rl == 1 && norm);
-}
-
-int launch_rows_screen(const AssignParams& p, int rl, bool norm, int32_t* tile_seg, int32_t* seg_tiles, int64_t cap,
-                       hipStream_t st) {
-  const int shape = rows_shape();
-  const int R = shape == 883 ? 256 : 128;
-  launch_tiling(p, R, tile_seg, seg_tiles, cap, st);
-  const bool ok = shape == 883   ? launch_rows_w<8, 8, 3>(p, rl, norm, tile_seg, seg_tiles, st)
-                  : shape == 482 ? launch_rows_w<4, 8, 2>(p, rl, norm, tile_seg, seg_tiles, st)
-                                 : launch_rows_w<4, 4, 3>(p, rl, norm, tile_seg, seg_tiles, st);
+// R-row tile offsets in the compact-list area, the tile map in the tile_seg slot; compact work list
+int launch_rows_screen(const AssignParams& p, const AssignPlan& plan, int rl, bool norm, const AssignWorkspace& ws,
+                       int64_t cap, hipStream_t st) {
+  const int shape = plan.rows_shape;
+  launch_tiling(p, shape == 883 ? 256 : 128, ws.tile_seg, ws.work_idx, cap, st);
+  const bool ok = shape == 883   ? launch_rows_w<8, 8, 3>(p, rl, norm, ws.tile_seg, ws.work_idx, st)
+                  : shape == 482 ? launch_rows_w<4, 8, 2>(p, rl, norm, ws.tile_seg, ws.work_idx, st)
+                                 : launch_rows_w<4, 4, 3>(p, rl, norm, ws.tile_seg, ws.work_idx, st);
   return ok ? RQSID_OK : fail(RQSID_E_LAUNCH, "assign: row-resident screen launch failed (device query / LDS attribute)");
 }
 

@@ -30,6 +30,7 @@ constexpr int kSC = 32;                   // dims per chunk (128-B row pieces: g
 constexpr int kSDim = 512;                // the stream kernel's row width
 constexpr int kNch = kSDim / kSC;         // chunks per tile
 constexpr int kSentinel = -2;             // out_global of a row left to the re-score
+static_assert(kSDim == kPlanStreamDim, "assign_plan.h constants");
 
 // W waves per block (32 rows each), S ring stages.  Shapes: 8 x 3 (one block per CU) and 4 x 2 (two
 // blocks per CU: the other block's compute / epilogue covers this one's ring refill).
@@ -1171,136 +1172,52 @@ __global__ __launch_bounds__(256) void tile_seg_kernel(const int32_t* __restrict
   }
 }
 
-template <int NT, int RL, bool NORM, bool T3, int W, int S>
-bool launch_one(const AssignParams& p, const int32_t* tile_seg, const int32_t* seg_tiles, int64_t max_tiles,
-                hipStream_t st) {
-  using L = StreamLayout<NT, RL, NORM, T3, W, S>;
-  static bool attr[kMaxDevices] = {};
-  const int dev = current_device(), ncu = device_cu_count();
-  if (dev < 0 || !ncu) return false;
-  if (!attr[dev]) {
-    if (hipFuncSetAttribute((const void*)assign_stream_kernel<NT, RL, NORM, T3, W, S>,
-                            hipFuncAttributeMaxDynamicSharedMemorySize, L::kBytes) != hipSuccess)
-      return false;
-    attr[dev] = true;
-  }
-  int64_t g = (int64_t)ncu * L::kBlocks;  // persistent: every block resident at once
-  if (g > max_tiles) g = max_tiles;
-  g = g / 8 * 8;
-  if (g < 8) g = 8;
-  hipLaunchKernelGGL((assign_stream_kernel<NT, RL, NORM, T3, W, S>), dim3((unsigned)g), dim3(W * 64), L::kBytes, st,
-                     p, tile_seg, seg_tiles);
-  return true;
+// the streamed form <W waves, S stages>, or the ping-pong 8-wave form (PP), of one (NT, T3) pair
+template <int NT, bool T3, int W, int S, bool PP>
+bool launch_form(const AssignParams& p, int rl, bool norm, const int32_t* tile_seg, const int32_t* seg_tiles,
+                 int64_t max_tiles, hipStream_t st) {
+  return dispatch_rl_norm(rl, norm, [&](auto RL, auto NORM) {
+    if constexpr (PP) {  // one persistent 8-wave block per CU
+      return launch_persistent<assign_pp_kernel<NT, RL(), NORM(), T3>>(PPLayout<NT, RL(), NORM(), T3>::kBytes, 512, 1,
+                                                                        max_tiles, st, p, tile_seg, seg_tiles);
+    } else {
+      using L = StreamLayout<NT, RL(), NORM(), T3, W, S>;
+      return launch_persistent<assign_stream_kernel<NT, RL(), NORM(), T3, W, S>>(L::kBytes, W * 64, L::kBlocks, max_tiles,
+                                                                                 st, p, tile_seg, seg_tiles);
+    }
+  });
 }
 
-// block shape: RQSID_STREAM_SHAPE = 83 (8 waves x 3 stages, the default), 42 (4 waves x 2 stages) or
-// 88 (the ping-pong 8-wave form)
-int stream_shape() {
-  const char* e = getenv("RQSID_STREAM_SHAPE");
-  const int v = e ? atoi(e) : 83;
-  return v == 42 || v == 88 ? v : 83;
-}
-
-template <int NT, int RL, bool NORM, bool T3>
-bool launch_pp(const AssignParams& p, const int32_t* tile_seg, const int32_t* seg_tiles, int64_t max_tiles,
-               hipStream_t st) {
-  using L = PPLayout<NT, RL, NORM, T3>;
-  static bool attr[kMaxDevices] = {};
-  const int dev = current_device(), ncu = device_cu_count();
-  if (dev < 0 || !ncu) return false;
-  if (!attr[dev]) {
-    if (hipFuncSetAttribute((const void*)assign_pp_kernel<NT, RL, NORM, T3>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            L::kBytes) != hipSuccess)
-      return false;
-    attr[dev] = true;
-  }
-  int64_t g = ncu;  // one persistent 8-wave block per CU
-  if (g > max_tiles) g = max_tiles;
-  g = g / 8 * 8;
-  if (g < 8) g = 8;
-  hipLaunchKernelGGL((assign_pp_kernel<NT, RL, NORM, T3>), dim3((unsigned)g), dim3(512), L::kBytes, st, p, tile_seg,
-                     seg_tiles);
-  return true;
-}
-
-bool launch_pp_shape(const AssignParams& p, int nt, bool t3, int rl, bool norm, int32_t* tile_seg, int32_t* seg_tiles,
-                     int64_t cap, hipStream_t st) {
-  constexpr int R = 256;
-  hipLaunchKernelGGL(stream_tiles_kernel, dim3(1), dim3(1024), 0, st, p.seg_row_off, p.n_segments, R,
-                     (int64_t)(cap / R + p.n_segments), p.work_count ? p.work_count + kErrSlot : (int32_t*)nullptr, seg_tiles);
-  const int64_t max_tiles = cap / R + p.n_segments;
-  const unsigned tg = (unsigned)(max_tiles / 256 + 1 < 4096 ? max_tiles / 256 + 1 : 4096);
-  hipLaunchKernelGGL(tile_seg_kernel, dim3(tg), dim3(256), 0, st, seg_tiles, p.n_segments, cap, tile_seg);
-#define RQ_L(NT, RL, NORM, T3) return launch_pp<NT, RL, NORM, T3>(p, tile_seg, seg_tiles, max_tiles, st)
-  if (nt == 8) {
-    if (rl == 0) RQ_L(8, 0, false, false);
-    else if (rl == 1) { if (norm) RQ_L(8, 1, true, false); else RQ_L(8, 1, false, false); }
-    else { if (norm) RQ_L(8, 2, true, false); else RQ_L(8, 2, false, false); }
-  } else if (t3) {
-    if (rl == 0) RQ_L(4, 0, false, true);
-    else if (rl == 1) { if (norm) RQ_L(4, 1, true, true); else RQ_L(4, 1, false, true); }
-    else { if (norm) RQ_L(4, 2, true, true); else RQ_L(4, 2, false, true); }
-  } else {
-    if (rl == 0) RQ_L(4, 0, false, false);
-    else if (rl == 1) { if (norm) RQ_L(4, 1, true, false); else RQ_L(4, 1, false, false); }
-    else { if (norm) RQ_L(4, 2, true, false); else RQ_L(4, 2, false, false); }
-  }
-#undef RQ_L
-  return false;
-}
-
-template <int W, int S>
+// R-row tiling, then the form's build for (nt, t3): 8 tiles 1 term, 4 tiles 3 terms, 4 tiles 1 term
+template <int W, int S, bool PP>
 bool launch_shape(const AssignParams& p, int nt, bool t3, int rl, bool norm, int32_t* tile_seg, int32_t* seg_tiles,
                   int64_t cap, hipStream_t st) {
-  constexpr int R = W * 32;
-  hipLaunchKernelGGL(stream_tiles_kernel, dim3(1), dim3(1024), 0, st, p.seg_row_off, p.n_segments, R,
-                     (int64_t)(cap / R + p.n_segments), p.work_count ? p.work_count + kErrSlot : (int32_t*)nullptr, seg_tiles);
-  const int64_t max_tiles = cap / R + p.n_segments;  // bound on the R-row tiles
-  const unsigned tg = (unsigned)(max_tiles / 256 + 1 < 4096 ? max_tiles / 256 + 1 : 4096);
-  hipLaunchKernelGGL(tile_seg_kernel, dim3(tg), dim3(256), 0, st, seg_tiles, p.n_segments, cap, tile_seg);
-#define RQ_L(NT, RL, NORM, T3) return launch_one<NT, RL, NORM, T3, W, S>(p, tile_seg, seg_tiles, max_tiles, st)
-  if (nt == 8) {
-    if (rl == 0) RQ_L(8, 0, false, false);
-    else if (rl == 1) { if (norm) RQ_L(8, 1, true, false); else RQ_L(8, 1, false, false); }
-    else { if (norm) RQ_L(8, 2, true, false); else RQ_L(8, 2, false, false); }
-  } else if (t3) {
-    if (rl == 0) RQ_L(4, 0, false, true);
-    else if (rl == 1) { if (norm) RQ_L(4, 1, true, true); else RQ_L(4, 1, false, true); }
-    else { if (norm) RQ_L(4, 2, true, true); else RQ_L(4, 2, false, true); }
-  } else {
-    if (rl == 0) RQ_L(4, 0, false, false);
-    else if (rl == 1) { if (norm) RQ_L(4, 1, true, false); else RQ_L(4, 1, false, false); }
-    else { if (norm) RQ_L(4, 2, true, false); else RQ_L(4, 2, false, false); }
-  }
-#undef RQ_L
-  return false;
+  const int64_t max_tiles = launch_tiling(p, W * 32, tile_seg, seg_tiles, cap, st);
+  if (nt == 8) return launch_form<8, false, W, S, PP>(p, rl, norm, tile_seg, seg_tiles, max_tiles, st);
+  if (t3) return launch_form<4, true, W, S, PP>(p, rl, norm, tile_seg, seg_tiles, max_tiles, st);
+  return launch_form<4, false, W, S, PP>(p, rl, norm, tile_seg, seg_tiles, max_tiles, st);
 }
 
 }  // namespace
 
-bool stream_supported(int nt, bool t3, int rl, bool norm) {
-  (void)norm;
-  if (nt == 8) return !t3 && rl >= 0 && rl <= 2;
-  if (nt == 4) return rl >= 0 && rl <= 2;
-  return false;
-}
-
-void launch_tiling(const AssignParams& p, int R, int32_t* tile_seg, int32_t* seg_tiles, int64_t cap, hipStream_t st) {
-  hipLaunchKernelGGL(stream_tiles_kernel, dim3(1), dim3(1024), 0, st, p.seg_row_off, p.n_segments, R,
-                     (int64_t)(cap / R + p.n_segments), p.work_count ? p.work_count + kErrSlot : (int32_t*)nullptr, seg_tiles);
-  const int64_t max_tiles = cap / R + p.n_segments;
+int64_t launch_tiling(const AssignParams& p, int R, int32_t* tile_seg, int32_t* seg_tiles, int64_t cap, hipStream_t st) {
+  const int64_t max_tiles = cap / R + p.n_segments;  // bound on the R-row tiles
+  hipLaunchKernelGGL(stream_tiles_kernel, dim3(1), dim3(1024), 0, st, p.seg_row_off, p.n_segments, R, max_tiles,
+                     p.work_count ? p.work_count + kErrSlot : (int32_t*)nullptr, seg_tiles);
   const unsigned tg = (unsigned)(max_tiles / 256 + 1 < 4096 ? max_tiles / 256 + 1 : 4096);
   hipLaunchKernelGGL(tile_seg_kernel, dim3(tg), dim3(256), 0, st, seg_tiles, p.n_segments, cap, tile_seg);
+  return max_tiles;
 }
 
-int launch_stream_screen(const AssignParams& p, int nt, bool t3, int rl, bool norm, int32_t* tile_seg,
-                         int32_t* seg_tiles, int64_t cap, int shape, hipStream_t st) {
-  if (shape == 0) shape = stream_shape();
-  bool ok;
-  if (shape == 88) ok = launch_pp_shape(p, nt, t3, rl, norm, tile_seg, seg_tiles, cap, st);
-  else if (shape == 42) ok = launch_shape<4, 2>(p, nt, t3, rl, norm, tile_seg, seg_tiles, cap, st);
-  else ok = launch_shape<8, 3>(p, nt, t3, rl, norm, tile_seg, seg_tiles, cap, st);
-  return ok ? RQSID_OK : fail(RQSID_E_LAUNCH, "assign: stream screen launch failed (device query / LDS attribute)");
+// the 256-row (shape 42: 128-row) tile offsets live in the compact-list area until the compaction pass
+int launch_stream_screen(const AssignParams& p, const AssignPlan& plan, int rl, bool norm, const AssignWorkspace& ws,
+                         int64_t cap, hipStream_t st) {
+  const auto launch = plan.stream_shape == 88   ? launch_shape<8, 0, true>
+                      : plan.stream_shape == 42 ? launch_shape<4, 2, false>
+                                                : launch_shape<8, 3, false>;
+  return launch(p, plan.nt, plan.t3, rl, norm, ws.tile_seg, ws.work_idx, cap, st)
+             ? RQSID_OK
+             : fail(RQSID_E_LAUNCH, "assign: stream screen launch failed (device query / LDS attribute)");
 }
 
 }  // namespace rqsid
