@@ -21,7 +21,7 @@ LIB_PATH = PKG / "librqsid.so"
 SRCS = [PKG / "csrc" / "rqsid.hip", PKG / "csrc" / "assign.hip", PKG / "csrc" / "assign_stream.hip",
         PKG / "csrc" / "assign_resident.hip", PKG / "csrc" / "assign_rows.hip", PKG / "csrc" / "assign_pc.hip",
         PKG / "csrc" / "auction.hip",
-        PKG / "csrc" / "auction_seg.hip"]
+        PKG / "csrc" / "auction_seg.hip", PKG / "csrc" / "quant_error.hip"]
 DEPS = SRCS + [PKG / "csrc" / "internal.h", PKG / "csrc" / "assign_common.h", PKG / "csrc" / "assign_plan.h"]
 HEADER = REPO / "include" / "rqsid.h"
 # host-only I/O library (CSV reader): plain g++, no GPU code
@@ -56,6 +56,10 @@ SIGNATURES = {
                                c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                c_vp, c_vp, c_i32, c_vp, c_i64, c_vp]),
     "rqsid_residual": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i32, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp]),
+    "rqsid_quant_error_workspace_bytes": (c_i64, [c_i64]),
+    "rqsid_quant_error": (c_i32, [c_vp, c_i32, c_i64, c_i32, c_vp, c_i32, c_i32,
+                                  c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, c_vp,
+                                  c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "rqsid_scale_groups": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp]),
     "rqsid_centroid_tile_rows": (c_i32, []),
     "rqsid_centroid_accumulate": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_i64, c_vp, c_vp]),

@@ -50,6 +50,17 @@ HIERARCHICAL_TRAIN = LevelSemantics(residual_from_weighted=True)
 SIMPLIFIED = LevelSemantics(normalize_residual=False, remap_last=False, last_group_mult="need_minus_2")
 
 
+@dataclass
+class QuantError:
+    """What ``RQEncoder.quant_error`` returns (device tensors)."""
+    ids: torch.Tensor        # i32 [N, L] semantic IDs the errors belong to
+    err: torch.Tensor        # f32 [N, L]: distance from level l's input vector to its assigned centre
+    x_norm: torch.Tensor     # f32 [N]: ||x||
+    recon_err: torch.Tensor  # f32 [N]: ||x - decode(ids, err)||, from the chain's own norms
+    sums: torch.Tensor       # f64 [L + 1]: per level sum of err^2 over the rows, then sum of ||x||^2
+    recon_levels: Optional[torch.Tensor] = None  # f32 [N, L]: recon_err had the chain stopped at level l
+
+
 class RQEncoder:
     def __init__(self, centers: Sequence[torch.Tensor], need_clusters: Sequence[int],
                  match: Optional[torch.Tensor] = None, group_dims: Sequence[int] = (),
@@ -68,6 +79,9 @@ class RQEncoder:
         self.pcs = [ops.prepare_centers(c.to(device)) for c in centers]
         self.cands: List[Optional[ops.Candidates]] = []
         self.has_penalty = False
+        self.n_groups = 1
+        self._last_raw: Optional[ops.Candidates] = None  # the last level's lists before deduplication
+        self._qws = None  # rqsid_quant_error workspace (sticky error word)
         for l in range(self.L):
             if l == 0:
                 c = ops.Candidates(torch.zeros(1, dtype=torch.int32, device=device),
@@ -78,6 +92,7 @@ class RQEncoder:
                 if match is not None and semantics.match_lookup:
                     m = match.to(device)
                     c = ops.match_to_candidates(m)
+                    self._last_raw = c  # position = rank among the allowed columns (quant_error / decode)
                     self.has_penalty = bool((c.count == 0).any().item())
                     self.n_groups = m.shape[0]
                 else:
@@ -108,7 +123,8 @@ class RQEncoder:
     def error_words(self):
         """Device views of the sticky error words this encoder's calls write (assign and bucketing)."""
         return ([self._ws.error_word()] if self._ws is not None else []) + \
-            [ops.bucket_error_word(w, s) for s, w in self._bws.items()]
+            [ops.bucket_error_word(w, s) for s, w in self._bws.items()] + \
+            ([self._qws.error_word()] if self._qws is not None else [])
 
     def check_errors(self) -> None:
         """Raise RuntimeError if any counter-driven write of this encoder's calls was dropped (one host sync)."""
@@ -257,3 +273,144 @@ class RQEncoder:
                 src = w if self.sem.residual_from_weighted else cur
                 cid = glob if self.sem.residual_global_id else out[l]
                 cur = ops.residual(src, self.pcs[l].centers, cid, self.group_dims, self.sem.normalize_residual)
+
+    # ------------------------------------------------------------------ quantisation error / decode
+    def global_rows(self, ids: torch.Tensor) -> List[torch.Tensor]:
+        """Per level the GLOBAL codebook row behind semantic IDs ``ids`` [N, L] (i32 [N] each; -1 where an id
+        does not name a centre): level 0 the id, a middle level ``parent * need[l] + id``, the last level the
+        ``id``-th allowed column of the group's match row (rank remap) or the raw column."""
+        if ids.dim() != 2 or ids.shape[1] != self.L:
+            raise ValueError(f"ids must be [N, {self.L}], got {tuple(ids.shape)}")
+        col = [ids[:, l].to(torch.int64) for l in range(self.L)]
+        out = []
+        for l in range(self.L):
+            if l == 0:
+                g = col[0]
+            elif l < self.L - 1:
+                ok = (col[l] >= 0) & (col[l] < self.need[l]) & (col[l - 1] >= 0)
+                g = torch.where(ok, col[l - 1] * self.need[l] + col[l], -1)
+            elif self._last_raw is not None and self.sem.remap_last:
+                c = self._last_raw
+                grp = col[l - 2] * self._last_mult() + col[l - 1]
+                gc = grp.clamp(0, self.n_groups - 1)
+                ok = (grp == gc) & (col[l] >= 0) & (col[l] < c.count.long()[gc])
+                pos = (c.base.long()[gc] + col[l]).clamp(0, c.idx.numel() - 1)
+                g = torch.where(ok, c.idx.long()[pos], -1)
+            else:
+                g = col[l]
+            out.append(g.to(torch.int32).contiguous())
+        return out
+
+    @property
+    def quant_error_fused(self) -> bool:
+        """rqsid_quant_error's domain: one dimension group, no weights, at most three levels."""
+        return self.L <= 3 and len(self.group_dims) == 1 and self.weights is None and not self.force_materialized
+
+    def quant_error(self, x: torch.Tensor, ids: Optional[torch.Tensor] = None,
+                    check: Optional[bool] = None) -> QuantError:
+        """Quantisation error of ``ids`` (default: ``encode(x)``) for the rows ``x``: per level the distance from the
+        level's input vector to the centre it was given, the row norms, the reconstruction error in the original
+        space and fp64 totals.  One streaming HIP pass (rqsid_quant_error) for one dimension group without weights
+        and L <= 3; otherwise the same quantities from ops.residual / ops.scale_groups and fp64 torch norms.
+        ``check`` as in ``encode``: an id that names no centre raises RuntimeError (its rows hold NaN)."""
+        if not self.sem.residual_global_id:
+            raise ValueError("quant_error: with residual_global_id=False the residual subtracts a centre other than "
+                             "the one assigned (the reference's predict quirk): the error of the encoding is undefined")
+        if check is None:
+            check = not torch.cuda.is_current_stream_capturing()
+        if x.dim() != 2 or x.shape[1] != self.dim:
+            raise ValueError(f"Input dimension {x.shape[-1]} does not match config embedding_dim {self.dim}")
+        if not (self.quant_error_fused and x.dtype in (torch.float16, torch.bfloat16)):
+            x = x.float()
+        x = x.contiguous()
+        if ids is None:
+            ids = self.encode(x, check=check)
+        else:
+            ids = ids.to(device=x.device, dtype=torch.int32)
+            if self.L == 2:
+                raise IndexError("list index out of range")  # as encode: the reference has no two-level form
+        if ids.shape[0] != x.shape[0]:
+            raise ValueError(f"ids has {ids.shape[0]} rows, x {x.shape[0]}")
+        glob = self.global_rows(ids)
+        n = x.shape[0]
+        if not self.quant_error_fused:
+            return self._quant_error_materialized(x, ids, glob, check)
+        order = None
+        if self.L == 3 and self._last_raw is not None and n > 0:
+            # process in the order of the last level's groups: c0 / c1 rows change once per group
+            grp = (ids[:, 0] * self._last_mult() + ids[:, 1]).clamp(0, self.n_groups - 1)
+            order = self._bucket(grp, self.n_groups).row_index
+        if self._qws is None:
+            self._qws = ops.QuantErrorWorkspace(n, self.device)
+        err, x_norm, sums = ops.quant_error(x, [pc.centers for pc in self.pcs], glob, self.sem.normalize_residual,
+                                            row_order=order, workspace=self._qws, check=False)
+        if check:
+            try:
+                ops.check_error_words([self._qws.error_word()], "RQEncoder.quant_error", ops.QUANT_ERROR_WORD)
+            except RuntimeError:
+                self._qws = None  # the word is sticky: the next call starts from a clean workspace
+                raise
+        rec = err.clone()
+        if self.sem.normalize_residual:
+            for l in range(1, self.L):
+                rec[:, l:] *= (err[:, l - 1] + 1e-8).unsqueeze(1)
+        return QuantError(ids, err, x_norm, rec[:, self.L - 1], sums, rec)
+
+    def _quant_error_materialized(self, x, ids, glob, check) -> QuantError:
+        """quant_error outside the kernel's domain (several groups, weights, L > 3): the chain of
+        _encode_materialized with every norm taken in fp64.  Original-space error: group g of level l's raw residual
+        stands for ``prod_{j<l} den_jg / prod_{j<=l} w_jg`` times as much of x (weights enter only when the
+        residuals are taken from the weighted data)."""
+        n, G = x.shape[0], len(self.group_dims)
+        dev = x.device
+        cur = x
+        err = torch.empty((n, self.L), dtype=torch.float32, device=dev)
+        rec = torch.empty((n, self.L), dtype=torch.float32, device=dev)
+        scale = torch.ones((n, G), dtype=torch.float64, device=dev)
+        bad = torch.zeros(n, dtype=torch.bool, device=dev)
+        for l in range(self.L):
+            w = self._weighted(cur, l)
+            src = w if self.sem.residual_from_weighted else cur
+            if self.sem.residual_from_weighted and self.weights is not None:
+                scale = scale / torch.tensor(self.weights[l], dtype=torch.float64, device=dev)
+            c = self.pcs[l].centers
+            bad |= (glob[l] < 0) | (glob[l] >= c.shape[0])
+            d = ops.residual(src, c, glob[l], self.group_dims, normalize=False)
+            gs = torch.stack([blk.double().pow(2).sum(1) for blk in d.split(self.group_dims, dim=1)], 1)
+            err[:, l] = gs.sum(1).sqrt().float()
+            rec[:, l] = (gs * scale * scale).sum(1).sqrt().float()
+            err[bad, l] = float("nan")
+            rec[bad, l] = float("nan")
+            if l < self.L - 1:
+                if self.sem.normalize_residual:
+                    scale = scale * (gs.sqrt().float() + 1e-8).double()
+                cur = ops.residual(src, c, glob[l], self.group_dims, self.sem.normalize_residual)
+        x_norm = x.double().pow(2).sum(1).sqrt().float()
+        good = ~bad
+        sums = torch.cat([err[good].double().pow(2).sum(0), x_norm[good].double().pow(2).sum().reshape(1)])
+        if check and bool(bad.any().item()):
+            raise RuntimeError("RQEncoder.quant_error: an id names no centre")
+        return QuantError(ids, err, x_norm, rec[:, self.L - 1], sums, rec)
+
+    def decode(self, ids: torch.Tensor, err: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Reconstruction f32 [N, D] of semantic IDs (plain torch gathers).  Plain residuals: the sum of the levels'
+        centres.  Normalised residuals: ``c0 + d0 (c1 + d1 c2)`` with ``d_l = err[:, l] + 1e-8`` from ``quant_error``
+        (the divisors are not recoverable from the IDs, so ``err`` is required)."""
+        if not self.sem.residual_global_id:
+            raise ValueError("decode: undefined with residual_global_id=False (see quant_error)")
+        if self.weights is not None or (self.sem.normalize_residual and len(self.group_dims) != 1):
+            raise ValueError("decode: one dimension group without weights only")
+        if self.sem.normalize_residual and self.L > 1 and err is None:
+            raise ValueError("decode: normalised residuals need err (quant_error's per-level norms)")
+        ids = ids.to(device=self.device, dtype=torch.int32)
+        glob = self.global_rows(ids)
+        for l, g in enumerate(glob):
+            if g.numel() and (int(g.min().item()) < 0 or int(g.max().item()) >= self.pcs[l].k):
+                raise IndexError(f"decode: a level-{l} id names no centre")
+        rows = [self.pcs[l].centers[glob[l].long()] for l in range(self.L)]
+        out = rows[self.L - 1]
+        for l in range(self.L - 2, -1, -1):
+            if self.sem.normalize_residual:
+                out = out * (err[:, l].to(self.device).float() + 1e-8).unsqueeze(1)
+            out = rows[l] + out
+        return out

@@ -867,6 +867,21 @@ class HierarchicalRQKMeans:
             return torch.zeros((0, L), dtype=torch.int32, device=self.device)
         return self._encoder(reference_quirks).encode(x)
 
+    def quantization_error(self, X: np.ndarray, return_rows: bool = False) -> Dict:
+        """How well the training-consistent IDs (``predict(X, reference_quirks=False)``) stand for the rows: per
+        level the mean squared distance to the assigned centre, the original-space reconstruction error and its
+        share of the rows' energy, plus the ID-usage figures of training_statistics.json (quant_report.py has the
+        keys).  The reference has no counterpart.  Rows cross to the device as in ``predict``; with a process
+        group each rank takes its shard and every rank returns the same dict."""
+        if not self.is_trained or not self.cluster_centers_list:
+            raise RuntimeError("Model not trained. Call train() first or load a trained model.")
+        if X.shape[1] != self.config.embedding_dim:
+            raise ValueError(f"Input dimension {X.shape[1]} does not match config embedding_dim "
+                             f"{self.config.embedding_dim}")
+        from .quant_report import quantization_report, shard_rows
+        x, comm = shard_rows(X, self.device, self.group)
+        return quantization_report(self._encoder(False), x, comm, return_rows)
+
     def gather_ids(self, ids_local: torch.Tensor) -> torch.Tensor:
         """All ranks' IDs in row order (one variable-size all_gather of int32 rows)."""
         if self.group is None:

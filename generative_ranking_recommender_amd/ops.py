@@ -235,16 +235,18 @@ class AssignWorkspace:
         return self.buf[240:244].view(torch.int32)
 
 
-def check_error_words(words, what: str) -> None:
-    """One host sync over device error words (AssignWorkspace / Buckets); raise if any is non-zero: a
-    counter-driven write was dropped, so the IDs of that call are not trustworthy."""
+def check_error_words(words, what: str, meaning: Optional[str] = None) -> None:
+    """One host sync over device error words (AssignWorkspace / Buckets / QuantErrorWorkspace); raise if any is
+    non-zero: a counter-driven write was dropped, so the IDs of that call are not trustworthy (``meaning``: what a
+    set word says when it is not one of those)."""
     ws = [w for w in words if w is not None]
     if not ws:
         return
     vals = torch.cat(ws).cpu().tolist()
     if any(vals):
-        raise RuntimeError(f"{what}: a device error word is set ({vals}): a counter-driven list write fell outside "
-                           "its slot and was dropped (csrc/assign_common.h kErrSlot, rqsid_bucket)")
+        raise RuntimeError(f"{what}: a device error word is set ({vals}): " + (meaning or (
+            "a counter-driven list write fell outside "
+            "its slot and was dropped (csrc/assign_common.h kErrSlot, rqsid_bucket)")))
 
 
 @dataclass
@@ -337,6 +339,69 @@ def residual(x: torch.Tensor, centers: torch.Tensor, ids: torch.Tensor, group_di
     _lib.check(lib().rqsid_residual(_ptr(x), n, d, _ptr(centers), centers.shape[0], _ptr(ids), _ptr(g), len(gd), int(normalize),
                                     _ptr(out), _stream()), "rqsid_residual")
     return out
+
+
+QUANT_ERROR_WORD = ("1: an id lies outside its codebook (that row's err is NaN from that level on and it is left out "
+                    "of the sums), 2: a row_order entry lies outside the rows (include/rqsid.h rqsid_quant_error)")
+
+
+class QuantErrorWorkspace:
+    """Scratch of rqsid_quant_error: per-block fp64 partial sums and, in bytes [0, 4), the sticky error word
+    (1: an id outside its codebook, 2: a row_order entry outside the rows), zeroed here once."""
+
+    def __init__(self, n_rows: int, device):
+        self.bytes = int(lib().rqsid_quant_error_workspace_bytes(n_rows))
+        self.buf = torch.empty(self.bytes, dtype=torch.uint8, device=device)
+        self.buf[:256].zero_()
+        self.n_rows = n_rows
+
+    def error_word(self) -> torch.Tensor:
+        return self.buf[:4].view(torch.int32)
+
+
+def quant_error(x: torch.Tensor, centers: Sequence[torch.Tensor], ids: Sequence[torch.Tensor],
+                normalize: bool = True, row_order: Optional[torch.Tensor] = None, want_x_norm: bool = True,
+                want_sums: bool = True, workspace: Optional[QuantErrorWorkspace] = None,
+                check: Optional[bool] = None):
+    """Quantisation error of an encoding in one pass over the rows (include/rqsid.h rqsid_quant_error).
+
+    ``x``: float32 / float16 / bfloat16 [N, D]; ``centers[l]``: f32 [K_l, D]; ``ids[l]``: i32 [N], the GLOBAL row of
+    ``centers[l]`` each row was given; ``row_order``: i32 [N] permutation that only sets the processing order.
+    Returns ``(err, x_norm, sums)``: err f32 [N, L] (a transposed view of the level-major buffer), x_norm f32 [N]
+    or None, sums f64 [L + 1] or None.  ``check`` (default: on unless the stream is being captured): read the
+    workspace's error word after the call (one host sync) and raise RuntimeError if an id was out of range."""
+    if check is None:
+        check = not torch.cuda.is_current_stream_capturing()
+    L = len(centers)
+    if L != len(ids) or not 1 <= L <= 3:
+        raise ValueError(f"rqsid_quant_error takes 1..3 levels with one id vector each, not {L} / {len(ids)}")
+    x_format = ROW_FORMATS.get(x.dtype)
+    if x_format is None:
+        raise ValueError(f"rqsid_quant_error reads float32, float16 or bfloat16 rows, not {x.dtype}")
+    _require_device(x, row_order, *centers, *ids)
+    n, d = x.shape
+    for c, i in zip(centers, ids):
+        if c.dtype != torch.float32 or c.dim() != 2 or c.shape[1] != d:
+            raise ValueError("rqsid_quant_error: centres must be float32 [K, D] with the rows' D")
+        if i.dtype != torch.int32 or i.numel() != n:
+            raise ValueError("rqsid_quant_error: ids must be int32 [N]")
+    if row_order is not None and (row_order.dtype != torch.int32 or row_order.numel() != n):
+        raise ValueError("rqsid_quant_error: row_order must be int32 [N]")
+    dev = x.device
+    err = torch.empty((L, n), dtype=torch.float32, device=dev)
+    x_norm = torch.empty(n, dtype=torch.float32, device=dev) if want_x_norm else None
+    sums = torch.empty(L + 1, dtype=torch.float64, device=dev) if want_sums else None
+    if workspace is None:
+        workspace = QuantErrorWorkspace(n, dev)
+    lv = []
+    for l in range(3):
+        lv += [_ptr(centers[l]), centers[l].shape[0], _ptr(ids[l])] if l < L else [None, 0, None]
+    _lib.check(lib().rqsid_quant_error(_ptr(x), x_format, n, d, _ptr(row_order), L, int(normalize), *lv,
+                                       _ptr(err), _ptr(x_norm), _ptr(sums), _ptr(workspace.buf), workspace.bytes,
+                                       _stream()), "rqsid_quant_error")
+    if check:
+        check_error_words([workspace.error_word()], "rqsid_quant_error", QUANT_ERROR_WORD)
+    return err.t(), x_norm, sums
 
 
 def scale_groups(x: torch.Tensor, group_dims: Sequence[int], weights: Sequence[float]) -> torch.Tensor:

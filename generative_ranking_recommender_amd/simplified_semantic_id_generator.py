@@ -254,6 +254,35 @@ class SimplifiedHierarchicalRQ:
         _, glob = masked_assign(data, candidate_centers, sub, cand, m.shape[0])
         return glob.long()
 
+    def quantization_error(self, X: np.ndarray, return_rows: bool = False) -> Dict:
+        """How well the trained codebooks' IDs stand for the rows ``X`` (quant_report.py has the keys; plain
+        residuals, raw last-level columns: the IDs ``train_rows`` produced).  The reference has no counterpart.
+        One or three levels (the trainer keeps only the last middle layer's centres)."""
+        from .encode import SIMPLIFIED, RQEncoder
+        from .quant_report import quantization_report, shard_rows
+        cfg = self.config
+        L = len(cfg.layer_clusters)
+        if not self.trained_kmeans_models or self.trained_kmeans_models[0] is None:
+            raise RuntimeError("Model not trained. Call train() first or load a trained model.")
+        if L not in (1, 3):
+            raise ValueError(f"quantization_error: {L} levels (the simplified model keeps centres for 1 or 3)")
+        if X.shape[1] != cfg.embedding_dim:
+            raise ValueError(f"Input dimension {X.shape[1]} does not match config embedding_dim {cfg.embedding_dim}")
+        centers = [self.trained_kmeans_models[0].cluster_centers]
+        if L == 3:
+            centers += [self.middle_layer_centers, self.final_layer_centers]
+        key = tuple((id(c), getattr(c, "_version", 0)) for c in centers) + (id(self.dynamic_match_matrix),)
+        cache = getattr(self, "_qe_encoder", None)
+        if cache is None or cache[0] != key:
+            match = None
+            if L == 3:
+                match = torch.as_tensor(np.asarray(self.dynamic_match_matrix)).to(torch.uint8)
+            enc = RQEncoder([c.float() for c in centers], cfg.need_clusters, match=match, semantics=SIMPLIFIED,
+                            device=self.device)
+            cache = self._qe_encoder = (key, enc, centers)  # holds the tensors: their ids stay theirs
+        x, _ = shard_rows(X, self.device)
+        return quantization_report(cache[1], x, None, return_rows)
+
     def save_model(self, path: str):
         """:333-343 (npz): centres of layer 0, middle and final layers + the match matrix."""
         arrays = {"config": np.frombuffer(json.dumps(asdict(self.config)).encode(), dtype=np.uint8)}

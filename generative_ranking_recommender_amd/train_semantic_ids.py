@@ -30,8 +30,12 @@ logger = logging.getLogger(__name__)
 class SemanticIDTrainer:
     """train_semantic_ids.py:35-365."""
 
-    def __init__(self, config, use_test_config: bool = False, device=None, group=None):
+    def __init__(self, config, use_test_config: bool = False, device=None, group=None,
+                 report_quantization: bool = False):
         self.config = config
+        # opt-in: also write quantization_report.json (HierarchicalRQKMeans.quantization_error of the training
+        # rows) next to training_statistics.json; the reference has no such file
+        self.report_quantization = report_quantization
         self.use_test_config = use_test_config
         self.rqkmeans_config = config.h_rqkmeans_test if use_test_config else config.h_rqkmeans
         self.device = device
@@ -76,7 +80,14 @@ class SemanticIDTrainer:
             self._save_semantic_ids(semantic_ids)
             stats = self._generate_statistics(semantic_ids)
             self._save_statistics(stats)
-        return {"model": model, "semantic_ids": semantic_ids, "statistics": stats, "song_ids": song_ids}
+        result = {"model": model, "semantic_ids": semantic_ids, "statistics": stats, "song_ids": song_ids}
+        if self.report_quantization:
+            # every rank takes part (sharded rows, all-reduced sums); fp16 rows cross to the device as they are
+            report = model.quantization_error(vectors)
+            if self.rank == 0:
+                rq_io.write_json(str(self.output_dir / "quantization_report.json"), report)
+            result["quantization_report"] = report
+        return result
 
     def _generate_semantic_ids(self, song_ids: list, train_result: Dict) -> Dict:
         """:209-237 (one host copy per level instead of a per-element .item() loop; a song id repeated in

@@ -173,6 +173,37 @@ int rqsid_residual(const float* x, int64_t n, int32_t dim, const float* centers,
                    const int32_t* center_id, const int32_t* group_dims, int32_t n_groups,
                    int32_t normalize, float* out, void* stream);
 
+/* Quantisation error of an encoding: one streaming pass that rebuilds the residual chain of IDs that are already
+ * chosen, with the fp32 operation sequence of _compute_residuals_with_centers (hierarchical_rq_kmeans.py:1088-1128,
+ * res_normalize != 0) or of the simplified generator's plain residuals (simplified_semantic_id_generator.py:78-96,
+ * 164-168, res_normalize == 0), one dimension group:
+ *   r0 = x - c0[id0];  e0 = fl32(sqrt(sum (double)r0_i^2));  v1 = res_normalize ? r0 / (e0 + 1e-8f) : r0;
+ *   r1 = v1 - c1[id1]; e1 likewise; ...
+ * so e_l is the distance from level l's input vector to its assigned centre, and e_l + 1e-8f the next level's
+ * divisor (the den_out of rqsid_assign's fused level 1).  x: [n_rows][dim] in x_format (RQSID_X_*, 16-byte aligned,
+ * 16-bit rows widened as they load: no fp32 copy); dim % 32 == 0, dim <= 1024; n_levels 1..3, levels beyond it take
+ * NULL / 0.  idL[row] is the GLOBAL row of cL assigned to that row (indexed by row).  row_order: NULL or a
+ * permutation of the rows that only sets the order they are processed in (e.g. rqsid_bucket's row_index by the last
+ * level's group: centre rows of the earlier levels are then re-read once per group); no per-row output depends on it.
+ * Outputs: err [n_levels][n_rows] level-major (required); x_norm [n_rows] = fl32(sqrt(sum (double)x_i^2)) (may be
+ * NULL); sums double[n_levels + 1] (may be NULL) = per level the sum over rows of (double)e_l^2, then the sum of
+ * (double)x_norm^2, added in a fixed order (per-block partials in the workspace, then a one-block kernel: no float
+ * atomics), bit-identical between two calls with the same inputs and row_order.
+ * A row whose id at some level is outside [0, kL) reads centre row 0 there instead (no address is formed from the
+ * id), gets NaN in err at that level and every later one, and is left out of every entry of sums.
+ * Workspace bytes [0, 4) are a sticky error word the caller zeroes when it allocates the workspace (a call never
+ * clears it): value 1 = an id out of range, 2 = a row_order entry outside [0, n_rows) (that position is skipped).
+ * RQSID_E_ARG / RQSID_E_WORKSPACE before any HIP call; n_rows == 0 succeeds and zeroes sums. */
+int64_t rqsid_quant_error_workspace_bytes(int64_t n_rows);
+int rqsid_quant_error(const void* x, int32_t x_format, int64_t n_rows, int32_t dim,
+                      const int32_t* row_order,
+                      int32_t n_levels, int32_t res_normalize,
+                      const float* c0, int32_t k0, const int32_t* id0,
+                      const float* c1, int32_t k1, const int32_t* id1,
+                      const float* c2, int32_t k2, const int32_t* id2,
+                      float* err, float* x_norm, double* sums,
+                      void* workspace, int64_t workspace_bytes, void* stream);
+
 /* y = x * w_g per dimension group (hierarchical_rq_kmeans.py:583-604). */
 int rqsid_scale_groups(const float* x, int64_t n, int32_t dim, const int32_t* group_dims,
                        int32_t n_groups, const float* weights, float* out, void* stream);
