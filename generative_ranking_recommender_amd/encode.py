@@ -61,6 +61,38 @@ class QuantError:
     recon_levels: Optional[torch.Tensor] = None  # f32 [N, L]: recon_err had the chain stopped at level l
 
 
+@dataclass
+class TopK:
+    """What ``RQEncoder.encode_topk`` returns (device tensors; the [N, L, k] ones are permuted views of the
+    level-major buffers the kernel writes).  Level l ranks the allowed centres of the segment the greedy path
+    reached (``ids[:, :l]``) for the level's own input vector, by (fp64 squared distance, list position)."""
+    ids: torch.Tensor    # i32 [N, L], equal to encode(x)
+    local: torch.Tensor  # i32 [N, L, k]: the id each place would have given (local[:, :, 0] == ids); -1: no such place
+    glob: torch.Tensor   # i32 [N, L, k]: its codebook row
+    dist: torch.Tensor   # f32 [N, L, k]: its distance (dist[:, l, 0] is the level's quantisation distance)
+
+
+class _TopKLevels:
+    """Collects rqsid_assign_topk's outputs level by level while an encode runs (RQEncoder.encode_topk)."""
+
+    def __init__(self, enc, n, k, device):
+        self.enc, self.k = enc, k
+        self.local = torch.empty((enc.L, n, k), dtype=torch.int32, device=device)
+        self.glob = torch.empty((enc.L, n, k), dtype=torch.int32, device=device)
+        self.dist = torch.empty((enc.L, n, k), dtype=torch.float32, device=device)
+
+    def level(self, l, x, buckets, fused=None):
+        enc = self.enc
+        if fused is not None and fused.den_out is not None:  # the assign of this level has written it
+            fused = ops.FusedResidual(fused.levels, fused.normalize, fused.ca, fused.seg_ca, fused.cb, fused.seg_cb,
+                                      fused.den_in, None)
+        ops.assign_topk(x, enc.pcs[l], buckets, enc.raw_cands[l], self.k, fused=fused, workspace=enc._tws,
+                        check=False, out=(self.local[l], self.glob[l], self.dist[l]))
+        last_raw_column = l == enc.L - 1 and l > 0 and not (enc.sem.match_lookup and enc.sem.remap_last)
+        if l == 0 or last_raw_column:  # these levels' ids are codebook rows
+            self.local[l].copy_(self.glob[l])
+
+
 class RQEncoder:
     def __init__(self, centers: Sequence[torch.Tensor], need_clusters: Sequence[int],
                  match: Optional[torch.Tensor] = None, group_dims: Sequence[int] = (),
@@ -82,6 +114,9 @@ class RQEncoder:
         self.n_groups = 1
         self._last_raw: Optional[ops.Candidates] = None  # the last level's lists before deduplication
         self._qws = None  # rqsid_quant_error workspace (sticky error word)
+        self._tws = None  # rqsid_assign_topk workspace (sticky error word)
+        # every level's list as built, before the duplicates leave it: what encode_topk ranks
+        self.raw_cands: List[ops.Candidates] = []
         for l in range(self.L):
             if l == 0:
                 c = ops.Candidates(torch.zeros(1, dtype=torch.int32, device=device),
@@ -99,6 +134,7 @@ class RQEncoder:
                     k = self.pcs[l].k
                     c = ops.Candidates(torch.zeros(1, dtype=torch.int32, device=device),
                                        torch.full((1,), k, dtype=torch.int32, device=device), k)
+            self.raw_cands.append(c)
             # bitwise-duplicate centres can never be the first minimum: drop them from the lists
             self.cands.append(ops.dedup_candidates(c, self.pcs[l].centers))
         self._ws = None
@@ -124,7 +160,8 @@ class RQEncoder:
         """Device views of the sticky error words this encoder's calls write (assign and bucketing)."""
         return ([self._ws.error_word()] if self._ws is not None else []) + \
             [ops.bucket_error_word(w, s) for s, w in self._bws.items()] + \
-            ([self._qws.error_word()] if self._qws is not None else [])
+            ([self._qws.error_word()] if self._qws is not None else []) + \
+            ([self._tws.error_word()] if self._tws is not None else [])
 
     def check_errors(self) -> None:
         """Raise RuntimeError if any counter-driven write of this encoder's calls was dropped (one host sync)."""
@@ -185,6 +222,42 @@ class RQEncoder:
             self.check_errors()
         return out.t()
 
+    def encode_topk(self, x: torch.Tensor, k: int, check: Optional[bool] = None) -> TopK:
+        """``encode(x)`` and, per level, the k nearest allowed centres of the segment the greedy path reached, for
+        the level's own input vector (rqsid_assign_topk on the lists BEFORE deduplication, so duplicate centres
+        take their places; on the last level with ``remap_last`` the local id is the rank among the allowed
+        columns, as in ``encode``).  Fused encoders pass the fused residual chain (16-bit rows stay 16-bit);
+        everything else ranks the matrices ``_encode_materialized`` builds.  1 <= k <= ops.TOPK_MAX.  ``check`` as
+        in ``encode``."""
+        if check is None:
+            check = not torch.cuda.is_current_stream_capturing()
+        k = int(k)
+        if not 1 <= k <= ops.TOPK_MAX:
+            raise ValueError(f"encode_topk: k = {k} (1..{ops.TOPK_MAX})")
+        if x.dim() != 2 or x.shape[1] != self.dim:
+            raise ValueError(f"Input dimension {x.shape[-1]} does not match config embedding_dim {self.dim}")
+        if not (self.fused and x.dtype in (torch.float16, torch.bfloat16)):
+            x = x.float()
+        x = x.contiguous()
+        self.last_row_format = ops.ROW_FORMAT_NAMES[x.dtype]
+        if self.L == 2:
+            raise IndexError("list index out of range")  # as encode: the reference has no two-level form
+        n = x.shape[0]
+        out = torch.empty((self.L, n), dtype=torch.int32, device=x.device)
+        tk = _TopKLevels(self, n, k, x.device)
+        self.last_rescored = []
+        if n:
+            ws = self._workspace(n)
+            if self._tws is None:
+                self._tws = ops.TopKWorkspace(n, k, self.device)
+            if self.fused:
+                self._encode_fused(x, out, ws, False, tk)
+            else:
+                self._encode_materialized(x, out, ws, False, tk)
+            if check:
+                self.check_errors()
+        return TopK(out.t(), tk.local.permute(1, 0, 2), tk.glob.permute(1, 0, 2), tk.dist.permute(1, 0, 2))
+
     def _last_level_buckets(self, out, l, n, device):
         if self.sem.match_lookup:
             mult = self.need[l - 2] if self.sem.last_group_mult == "need_l_minus_2" else self.need[-2]
@@ -209,13 +282,15 @@ class RQEncoder:
                 # reference: mapping_result[prev_id][cur_id] KeyError (:1084)
                 raise KeyError(int(glob[bad[0, 0]].item()))
 
-    def _encode_fused(self, x, out, ws, count_rescored):
+    def _encode_fused(self, x, out, ws, count_rescored, tk=None):
         n = x.shape[0]
         dev = x.device
         norm = self.sem.normalize_residual
         # level 0 is one segment over every centre: the local id IS the global id
-        ops.assign(x, self.pcs[0], ops.single_segment(n, dev), self.cands[0], out_local=out[0], out_global=out[0],
-                   workspace=ws)
+        b = ops.single_segment(n, dev)
+        ops.assign(x, self.pcs[0], b, self.cands[0], out_local=out[0], out_global=out[0], workspace=ws)
+        if tk is not None:
+            tk.level(0, x, b)
         if count_rescored:
             self.last_rescored.append(ws.rescored())
         if self.L == 1:
@@ -225,6 +300,8 @@ class RQEncoder:
         b = self._bucket(out[0], self.need[0]) if self.L == 3 else self._last_level_buckets(out, 1, n, dev)
         fr1 = ops.FusedResidual(1, norm, self.pcs[0].centers, None, den_out=n1)
         ops.assign(x, self.pcs[1], b, self.cands[1], out_local=out[1], out_global=glob1, workspace=ws, fused=fr1)
+        if tk is not None:
+            tk.level(1, x, b, fr1)
         if count_rescored:
             self.last_rescored.append(ws.rescored())
         glob2 = torch.empty(n, dtype=torch.int32, device=dev)
@@ -232,6 +309,8 @@ class RQEncoder:
         seg_ca, seg_cb = self._last_segment_rows(dev)
         fr2 = ops.FusedResidual(2, norm, self.pcs[0].centers, seg_ca, self.pcs[1].centers, seg_cb, den_in=n1)
         ops.assign(x, self.pcs[2], b, self.cands[2], out_local=out[2], out_global=glob2, workspace=ws, fused=fr2)
+        if tk is not None:
+            tk.level(2, x, b, fr2)
         if count_rescored:
             self.last_rescored.append(ws.rescored())
         self._finish_last(out, 2, glob2)
@@ -250,7 +329,7 @@ class RQEncoder:
             self._seg_rows, self._seg_rows_key = (seg_ca, seg_cb), key
         return self._seg_rows
 
-    def _encode_materialized(self, x, out, ws, count_rescored):
+    def _encode_materialized(self, x, out, ws, count_rescored, tk=None):
         n = x.shape[0]
         cur = x
         glob = torch.empty(n, dtype=torch.int32, device=x.device)
@@ -267,6 +346,8 @@ class RQEncoder:
                 b = self._last_level_buckets(out, l, n, x.device)
                 ops.assign(w, self.pcs[l], b, self.cands[l], out_local=out[l], out_global=glob, workspace=ws)
                 self._finish_last(out, l, glob)
+            if tk is not None:
+                tk.level(l, w, b)
             if count_rescored:
                 self.last_rescored.append(ws.rescored())
             if l < self.L - 1:

@@ -882,6 +882,45 @@ class HierarchicalRQKMeans:
         x, comm = shard_rows(X, self.device, self.group)
         return quantization_report(self._encoder(False), x, comm, return_rows)
 
+    def predict_topk(self, X: np.ndarray, k: int, reference_quirks: bool = False):
+        """``predict`` plus the runners-up: ``(ids, alt_ids, dist)`` as numpy arrays, ids int64 [N, L] (equal to
+        ``predict(X, reference_quirks)``), alt_ids int64 [N, L, k] (the id each of the k nearest allowed centres of
+        the level would have given, -1 where the segment has fewer; ``alt_ids[:, :, 0] == ids``) and dist float32
+        [N, L, k] (``RQEncoder.encode_topk``).  Rows are sharded and the results all-gathered as in ``predict``."""
+        if not self.is_trained or not self.cluster_centers_list:
+            raise RuntimeError("Model not trained. Call train() first or load a trained model.")
+        if X.shape[1] != self.config.embedding_dim:
+            raise ValueError(f"Input dimension {X.shape[1]} does not match config embedding_dim "
+                             f"{self.config.embedding_dim}")
+        from .quant_report import shard_rows
+        x, comm = shard_rows(X, self.device, self.group)
+        L = len(self.config.layer_clusters)
+        if x.shape[0]:
+            tk = self._encoder(reference_quirks).encode_topk(x, k)
+            parts = [tk.ids.contiguous(), tk.local.contiguous(), tk.dist.contiguous()]
+        else:
+            parts = [torch.zeros((0, L), dtype=torch.int32, device=self.device),
+                     torch.zeros((0, L, int(k)), dtype=torch.int32, device=self.device),
+                     torch.zeros((0, L, int(k)), dtype=torch.float32, device=self.device)]
+        if comm is not None:
+            parts = [comm.all_gather_rows(t) for t in parts]
+        ids, alt, dist = (t.cpu().numpy() for t in parts)
+        return ids.astype(np.int64), alt.astype(np.int64), dist
+
+    def assignment_margins(self, X: np.ndarray) -> Dict:
+        """Per level, how far the second-nearest allowed centre is behind the chosen one for the training-consistent
+        IDs (margin_report.py has the keys).  With a process group each rank takes its shard and every rank
+        returns the same dict."""
+        if not self.is_trained or not self.cluster_centers_list:
+            raise RuntimeError("Model not trained. Call train() first or load a trained model.")
+        if X.shape[1] != self.config.embedding_dim:
+            raise ValueError(f"Input dimension {X.shape[1]} does not match config embedding_dim "
+                             f"{self.config.embedding_dim}")
+        from .margin_report import margin_report
+        from .quant_report import shard_rows
+        x, comm = shard_rows(X, self.device, self.group)
+        return margin_report(self._encoder(False), x, comm)
+
     def gather_ids(self, ids_local: torch.Tensor) -> torch.Tensor:
         """All ranks' IDs in row order (one variable-size all_gather of int32 rows)."""
         if self.group is None:

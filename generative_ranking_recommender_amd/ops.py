@@ -321,6 +321,87 @@ def nearest(x: torch.Tensor, pc: PreparedCenters, workspace: Optional[AssignWork
         pc.nearest_cand = dedup_candidates(cand, pc.centers) if pc.k > kMaxList else cand
     return assign(x, pc, b, pc.nearest_cand, workspace=workspace, screen_terms=screen_terms)[1]
 
+TOPK_MAX = 8  # RQSID_TOPK_MAX (include/rqsid.h)
+TOPK_WORD = ("1: the device tile count exceeded max_tiles (tiles beyond were not ranked), 2: a row position or "
+             "row_index entry outside the rows (skipped), 4: a candidate's centre row outside the table "
+             "(include/rqsid.h rqsid_assign_topk)")
+
+
+class TopKWorkspace:
+    """Header of rqsid_assign_topk: bytes [0, 4) the sticky error word (zeroed here once, never by a call), bytes
+    [4, 16) the three per-call counters."""
+
+    def __init__(self, n_rows: int, k: int, device):
+        self.bytes = int(lib().rqsid_assign_topk_workspace_bytes(n_rows, k))
+        self.buf = torch.empty(self.bytes, dtype=torch.uint8, device=device)
+        self.buf[:16].zero_()
+        self.n_rows, self.k = n_rows, k
+
+    def error_word(self) -> torch.Tensor:
+        return self.buf[:4].view(torch.int32)
+
+    def counters(self) -> dict:
+        """The last call's counters (host sync): rows ranked from their list, rows that took the all-candidate
+        pass, non-finite rows."""
+        a, b, c = self.buf[4:16].view(torch.int32).tolist()
+        return {"listed_rows": a, "all_candidate_rows": b, "nonfinite_rows": c}
+
+
+def assign_topk(x: torch.Tensor, pc: PreparedCenters, buckets: Buckets, cand: Candidates, k: int,
+                fused: Optional[FusedResidual] = None, workspace: Optional[TopKWorkspace] = None,
+                check: Optional[bool] = None, out=None):
+    """The k nearest allowed centres of every row (include/rqsid.h rqsid_assign_topk): ``(local, global, dist)``,
+    i32 / i32 / f32 [N, k], slot t = the t-th smallest (fp64 squared distance, list position).  ``cand`` is ranked as
+    given: pass the list before any removal of duplicate centres.  ``x``, ``buckets``, ``cand`` and ``fused`` as in
+    ``assign``.  ``check`` (default: on unless the stream is being captured): read the workspace's error word after
+    the call (one host sync) and raise RuntimeError if it is set.  ``out``: three [N, k] tensors to write into."""
+    if check is None:
+        check = not torch.cuda.is_current_stream_capturing()
+    _require_device(x, pc.centers, cand.base, cand.count, cand.idx, cand.flags, cand.lid)
+    x_format = ROW_FORMATS.get(x.dtype)
+    if x_format is None:
+        raise ValueError(f"rqsid_assign reads float32, float16 or bfloat16 rows, not {x.dtype}")
+    n, d = x.shape
+    if d != pc.centers.shape[1]:
+        raise ValueError(f"dimension mismatch: x has {d}, centres {pc.centers.shape[1]}")
+    k = int(k)
+    if not 1 <= k <= TOPK_MAX:
+        raise ValueError(f"rqsid_assign_topk: k = {k} (1..{TOPK_MAX})")
+    dev = x.device
+    if out is None:
+        out = (torch.empty((n, k), dtype=torch.int32, device=dev), torch.empty((n, k), dtype=torch.int32, device=dev),
+               torch.empty((n, k), dtype=torch.float32, device=dev))
+    loc, glob, dist = out
+    _require_device(loc, glob, dist)
+    if workspace is None:
+        workspace = TopKWorkspace(n, k, dev)
+    f = fused
+    if f is not None:
+        _require_device(f.ca, f.seg_ca, f.cb, f.seg_cb, f.den_in, f.den_out)
+    _lib.check(lib().rqsid_assign_topk(
+        _ptr(x), x_format, n, d, _ptr(buckets.row_index), buckets.n_segments, _ptr(buckets.seg_row_off),
+        _ptr(buckets.seg_tile_off), buckets.max_tiles, _ptr(pc.centers), _ptr(pc.meta), pc.k,
+        _ptr(cand.base), _ptr(cand.count), cand.count_max, _ptr(cand.idx), _ptr(cand.lid), _ptr(cand.flags),
+        0 if f is None else f.levels, 0 if f is None else int(f.normalize),
+        None if f is None else _ptr(f.ca), None if f is None else _ptr(f.seg_ca),
+        None if f is None else _ptr(f.cb), None if f is None else _ptr(f.seg_cb),
+        None if f is None else _ptr(f.den_in), None if f is None else _ptr(f.den_out),
+        k, _ptr(loc), _ptr(glob), _ptr(dist), _ptr(workspace.buf), workspace.bytes, _stream()), "rqsid_assign_topk")
+    if check:
+        check_error_words([workspace.error_word()], "rqsid_assign_topk", TOPK_WORD)
+    return loc, glob, dist
+
+
+def nearest_topk(x: torch.Tensor, pc: PreparedCenters, k: int, workspace: Optional[TopKWorkspace] = None,
+                 check: Optional[bool] = None):
+    """The k nearest of ALL centres of ``pc`` per row, one segment: ``(local, global, dist)`` [N, k] (local ==
+    global).  The raw table is
+    ranked (not ``pc.nearest_cand``, whose duplicate centres are removed: a duplicate is a valid second place)."""
+    n = x.shape[0]
+    cand = Candidates(torch.zeros(1, dtype=torch.int32, device=x.device),
+                      torch.full((1,), pc.k, dtype=torch.int32, device=x.device), pc.k)
+    return assign_topk(x, pc, single_segment(n, x.device), cand, k, workspace=workspace, check=check)
+
 
 def _groups_tensor(group_dims: Sequence[int], device) -> torch.Tensor:
     return torch.tensor(list(group_dims), dtype=torch.int32, device=device)

@@ -254,18 +254,16 @@ class SimplifiedHierarchicalRQ:
         _, glob = masked_assign(data, candidate_centers, sub, cand, m.shape[0])
         return glob.long()
 
-    def quantization_error(self, X: np.ndarray, return_rows: bool = False) -> Dict:
-        """How well the trained codebooks' IDs stand for the rows ``X`` (quant_report.py has the keys; plain
-        residuals, raw last-level columns: the IDs ``train_rows`` produced).  The reference has no counterpart.
-        One or three levels (the trainer keeps only the last middle layer's centres)."""
+    def _trained_encoder(self, what: str, X: np.ndarray):
+        """The RQEncoder of the trained codebooks (plain residuals, raw last-level columns), cached per codebook
+        identity; one or three levels (the trainer keeps only the last middle layer's centres)."""
         from .encode import SIMPLIFIED, RQEncoder
-        from .quant_report import quantization_report, shard_rows
         cfg = self.config
         L = len(cfg.layer_clusters)
         if not self.trained_kmeans_models or self.trained_kmeans_models[0] is None:
             raise RuntimeError("Model not trained. Call train() first or load a trained model.")
         if L not in (1, 3):
-            raise ValueError(f"quantization_error: {L} levels (the simplified model keeps centres for 1 or 3)")
+            raise ValueError(f"{what}: {L} levels (the simplified model keeps centres for 1 or 3)")
         if X.shape[1] != cfg.embedding_dim:
             raise ValueError(f"Input dimension {X.shape[1]} does not match config embedding_dim {cfg.embedding_dim}")
         centers = [self.trained_kmeans_models[0].cluster_centers]
@@ -280,8 +278,38 @@ class SimplifiedHierarchicalRQ:
             enc = RQEncoder([c.float() for c in centers], cfg.need_clusters, match=match, semantics=SIMPLIFIED,
                             device=self.device)
             cache = self._qe_encoder = (key, enc, centers)  # holds the tensors: their ids stay theirs
+        return cache[1]
+
+    def quantization_error(self, X: np.ndarray, return_rows: bool = False) -> Dict:
+        """How well the trained codebooks' IDs stand for the rows ``X`` (quant_report.py has the keys; plain
+        residuals, raw last-level columns: the IDs ``train_rows`` produced).  The reference has no counterpart.
+        One or three levels (the trainer keeps only the last middle layer's centres)."""
+        from .quant_report import quantization_report, shard_rows
+        enc = self._trained_encoder("quantization_error", X)
         x, _ = shard_rows(X, self.device)
-        return quantization_report(cache[1], x, None, return_rows)
+        return quantization_report(enc, x, None, return_rows)
+
+    def predict_topk(self, X: np.ndarray, k: int, reference_quirks: bool = False):
+        """The trained codebooks' IDs of the rows ``X`` and their runners-up: ``(ids, alt_ids, dist)`` as numpy
+        arrays, ids int64 [N, L], alt_ids int64 [N, L, k] (the id each of the k nearest allowed centres of the level
+        would have given, -1 where the segment has fewer; ``alt_ids[:, :, 0] == ids``), dist float32 [N, L, k]
+        (``RQEncoder.encode_topk``).  ``reference_quirks`` is accepted for symmetry with
+        ``HierarchicalRQKMeans.predict_topk``: the simplified model has one predict semantics."""
+        from .quant_report import shard_rows
+        enc = self._trained_encoder("predict_topk", X)
+        x, _ = shard_rows(X, self.device)
+        tk = enc.encode_topk(x, k)
+        return (tk.ids.cpu().numpy().astype(np.int64), tk.local.cpu().numpy().astype(np.int64),
+                tk.dist.contiguous().cpu().numpy())
+
+    def assignment_margins(self, X: np.ndarray) -> Dict:
+        """Per level, how far the second-nearest allowed centre is behind the chosen one (margin_report.py has the
+        keys)."""
+        from .margin_report import margin_report
+        from .quant_report import shard_rows
+        enc = self._trained_encoder("assignment_margins", X)
+        x, _ = shard_rows(X, self.device)
+        return margin_report(enc, x, None)
 
     def save_model(self, path: str):
         """:333-343 (npz): centres of layer 0, middle and final layers + the match matrix."""

@@ -31,8 +31,11 @@ class SemanticIDTrainer:
     """train_semantic_ids.py:35-365."""
 
     def __init__(self, config, use_test_config: bool = False, device=None, group=None,
-                 report_quantization: bool = False):
+                 report_quantization: bool = False, report_margins: bool = False):
         self.config = config
+        # opt-in: also write assignment_margin_report.json (HierarchicalRQKMeans.assignment_margins of the training
+        # rows) next to the other side files
+        self.report_margins = report_margins
         # opt-in: also write quantization_report.json (HierarchicalRQKMeans.quantization_error of the training
         # rows) next to training_statistics.json; the reference has no such file
         self.report_quantization = report_quantization
@@ -87,6 +90,11 @@ class SemanticIDTrainer:
             if self.rank == 0:
                 rq_io.write_json(str(self.output_dir / "quantization_report.json"), report)
             result["quantization_report"] = report
+        if self.report_margins:
+            margins = model.assignment_margins(vectors)  # every rank takes part, as above
+            if self.rank == 0:
+                rq_io.write_json(str(self.output_dir / "assignment_margin_report.json"), margins)
+            result["assignment_margin_report"] = margins
         return result
 
     def _generate_semantic_ids(self, song_ids: list, train_result: Dict) -> Dict:

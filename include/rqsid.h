@@ -165,6 +165,51 @@ int rqsid_assign_x(const void* x, int32_t x_format, int64_t n_rows, int32_t dim,
                    int32_t* out_local, int32_t* out_global, int32_t screen_terms,
                    void* workspace, int64_t workspace_bytes, void* stream);
 
+/* The k nearest allowed centres of every row, exactly: rqsid_assign's question asked for the first k places.
+ * Segments, tiles (rqsid_bucket with rqsid_assign_tile_rows()), candidate lists, x_format and the fused residual
+ * chain (res_levels, res_normalize, ca / seg_ca, cb / seg_cb, den_in, den_out) mean exactly what they mean for
+ * rqsid_assign_x, so the same tables serve both calls; den_out (res_levels 1, res_normalize) receives
+ * fl32(sqrt(fp64 sum)) + 1e-8f as there.  The row's vector v is built with the fp32 operation sequence of
+ * rqsid_assign's exact re-score (bit-identical to rqsid_residual's rows at res_levels 0).
+ * Outputs, all [n_rows][k] row-major and indexed by row: slot t of a row of segment s holds the allowed centre with
+ * the t-th smallest key (d2, position in the segment's list), d2 = sum_i ((double)v_i - (double)c_i)^2:
+ * out_dist = fl32(sqrt(d2)), out_local = cand_lid[cand_base[s] + position] (cand_lid NULL: the position), out_global =
+ * the centre row.  A list is ranked as given: bitwise-duplicate centres each take their place (pass the list
+ * BEFORE any removal of duplicates).  Slot 0 therefore equals rqsid_assign's out_local / out_global on every row
+ * whose distances are finite and whose segment is not a penalty segment.
+ *  - slots t >= cand_count[s]: -1 / -1 / +inf;
+ *  - a segment flagged RQSID_SEG_PENALTY has no allowed centre to rank: every slot of its rows -1 / -1 / +inf;
+ *  - a row with a non-finite element of v, or a non-finite distance: -1 / -1 / NaN in every slot; it is counted
+ *    (below) and is not an error.
+ * Limits: 1 <= k <= RQSID_TOPK_MAX; dim % 32 == 0, dim <= 1024; x and centers 16-byte aligned; n_rows == 0 succeeds
+ * without touching anything.  RQSID_E_ARG / RQSID_E_WORKSPACE before any HIP call.  Stream-ordered, no host
+ * synchronisation, graph-capturable, no float atomics: two calls on the same inputs give identical bytes.
+ * Method: per 128-row tile an fp32 screen on v_mfma_f32_32x32x2_f32 with a rigorous interval per
+ * candidate, a per-row list of the candidates whose lower end does not exceed the k-th smallest upper end, and an
+ * fp64 pass over the list; a row whose list overflows (many exact ties) takes the fp64 pass over all its candidates.
+ * The result never depends on the interval's width, only the amount of fp64 work.
+ * Workspace (rqsid_assign_topk_workspace_bytes; every list lives in LDS, so it is the header alone):
+ *   bytes [0, 4)   sticky error word, zeroed by the caller at allocation and never cleared by a call.  No write of
+ *                  this entry point takes its position from a device counter; the word records indices read from
+ *                  device tables that were clamped instead of followed: 1 = the tile count seg_tile_off[n_segments]
+ *                  exceeded max_tiles (the tiles beyond are not processed), 2 = a row position or row_index entry
+ *                  outside [0, n_rows) (skipped), 4 = a candidate's centre row outside [0, n_centers) (centre row 0
+ *                  is read instead; no address is formed from it);
+ *   bytes [4, 16)  three int32 counters zeroed by every call: rows ranked from their list, rows that took the
+ *                  all-candidate pass, non-finite rows. */
+#define RQSID_TOPK_MAX 8
+int64_t rqsid_assign_topk_workspace_bytes(int64_t n_rows, int32_t k);
+int rqsid_assign_topk(const void* x, int32_t x_format, int64_t n_rows, int32_t dim, const int32_t* row_index,
+                      int32_t n_segments, const int32_t* seg_row_off, const int32_t* seg_tile_off, int64_t max_tiles,
+                      const float* centers, const float* c_meta, int32_t n_centers,
+                      const int32_t* cand_base, const int32_t* cand_count, int32_t cand_count_max,
+                      const int32_t* cand_idx, const int32_t* cand_lid, const uint8_t* seg_flags,
+                      int32_t res_levels, int32_t res_normalize,
+                      const float* ca, const int32_t* seg_ca, const float* cb, const int32_t* seg_cb,
+                      const float* den_in, float* den_out,
+                      int32_t k, int32_t* out_local, int32_t* out_global, float* out_dist,
+                      void* workspace, int64_t workspace_bytes, void* stream);
+
 /* Residual r = x - c[center_id[row]]; with normalize != 0 each dimension group
  * g is divided by (||r_g|| + 1e-8).  Replaces _compute_residuals_with_centers
  * (hierarchical_rq_kmeans.py:1088-1128) and the plain residuals of
