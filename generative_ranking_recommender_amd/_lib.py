@@ -21,8 +21,10 @@ LIB_PATH = PKG / "librqsid.so"
 SRCS = [PKG / "csrc" / "rqsid.hip", PKG / "csrc" / "assign.hip", PKG / "csrc" / "assign_stream.hip",
         PKG / "csrc" / "assign_resident.hip", PKG / "csrc" / "assign_rows.hip", PKG / "csrc" / "assign_pc.hip",
         PKG / "csrc" / "auction.hip",
-        PKG / "csrc" / "auction_seg.hip", PKG / "csrc" / "quant_error.hip", PKG / "csrc" / "assign_topk.hip"]
-DEPS = SRCS + [PKG / "csrc" / "internal.h", PKG / "csrc" / "assign_common.h", PKG / "csrc" / "assign_plan.h"]
+        PKG / "csrc" / "auction_seg.hip", PKG / "csrc" / "quant_error.hip", PKG / "csrc" / "assign_topk.hip",
+        PKG / "csrc" / "beam.hip"]
+DEPS = SRCS + [PKG / "csrc" / "internal.h", PKG / "csrc" / "assign_common.h", PKG / "csrc" / "assign_plan.h",
+               PKG / "csrc" / "topk_kernel.h"]
 HEADER = REPO / "include" / "rqsid.h"
 # host-only I/O library (CSV reader): plain g++, no GPU code
 IO_LIB_PATH = PKG / "librqsid_io.so"
@@ -61,6 +63,14 @@ SIGNATURES = {
                                   c_vp, c_vp, c_i32, c_vp, c_vp, c_vp,
                                   c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                   c_i32, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "rqsid_beam_expand_workspace_bytes": (c_i64, [c_i64, c_i32]),
+    "rqsid_beam_expand": (c_i32, [c_vp, c_i32, c_i64, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_i64,
+                                  c_vp, c_vp, c_i32,
+                                  c_vp, c_vp, c_i32, c_vp, c_vp, c_vp,
+                                  c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                  c_i32, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "rqsid_beam_merge": (c_i32, [c_i64, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                 c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "rqsid_residual": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i32, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp]),
     "rqsid_quant_error_workspace_bytes": (c_i64, [c_i64]),
     "rqsid_quant_error": (c_i32, [c_vp, c_i32, c_i64, c_i32, c_vp, c_i32, c_i32,

@@ -72,6 +72,16 @@ class TopK:
     dist: torch.Tensor   # f32 [N, L, k]: its distance (dist[:, l, 0] is the level's quantisation distance)
 
 
+@dataclass
+class Beam:
+    """What ``RQEncoder.encode_beam`` returns (device tensors)."""
+    ids: torch.Tensor        # i32 [N, L]: the best path
+    recon_err: torch.Tensor  # f32 [N]: its original-space reconstruction error ||x - x_hat||
+    paths: torch.Tensor      # i32 [N, B, L]: every slot's path (slot 0 is greedy; -1 in a dead slot)
+    path_err: torch.Tensor   # f32 [N, B]: every slot's error (+inf in a dead slot, NaN in a non-finite row)
+    slot: torch.Tensor       # i32 [N]: the slot ``ids`` came from
+
+
 class _TopKLevels:
     """Collects rqsid_assign_topk's outputs level by level while an encode runs (RQEncoder.encode_topk)."""
 
@@ -115,6 +125,7 @@ class RQEncoder:
         self._last_raw: Optional[ops.Candidates] = None  # the last level's lists before deduplication
         self._qws = None  # rqsid_quant_error workspace (sticky error word)
         self._tws = None  # rqsid_assign_topk workspace (sticky error word)
+        self._xws = None  # rqsid_beam_expand workspace (sticky error word)
         # every level's list as built, before the duplicates leave it: what encode_topk ranks
         self.raw_cands: List[ops.Candidates] = []
         for l in range(self.L):
@@ -161,7 +172,8 @@ class RQEncoder:
         return ([self._ws.error_word()] if self._ws is not None else []) + \
             [ops.bucket_error_word(w, s) for s, w in self._bws.items()] + \
             ([self._qws.error_word()] if self._qws is not None else []) + \
-            ([self._tws.error_word()] if self._tws is not None else [])
+            ([self._tws.error_word()] if self._tws is not None else []) + \
+            ([self._xws.error_word()] if self._xws is not None else [])
 
     def check_errors(self) -> None:
         """Raise RuntimeError if any counter-driven write of this encoder's calls was dropped (one host sync)."""
@@ -257,6 +269,111 @@ class RQEncoder:
             if check:
                 self.check_errors()
         return TopK(out.t(), tk.local.permute(1, 0, 2), tk.glob.permute(1, 0, 2), tk.dist.permute(1, 0, 2))
+
+    # ------------------------------------------------------------------ beam search
+    def _beam_tables(self, dev):
+        """Per level the candidate lists before deduplication plus the dead items' segment, and the last level's
+        per-group residual centre rows with that segment's entry (row 0) appended; built once."""
+        key = str(dev)
+        if getattr(self, "_beam_tables_key", None) != key:
+            cands = [ops.with_dead_segment(c) for c in self.raw_cands]
+            zero = torch.zeros(1, dtype=torch.int32, device=dev)
+            seg1 = torch.cat([torch.arange(self.need[0], dtype=torch.int32, device=dev), zero])
+            seg2 = None
+            if self.L == 3:
+                seg2 = tuple(torch.cat([t, zero]) for t in self._last_segment_rows(dev))
+            self._beam_tab, self._beam_tables_key = (cands, seg1, seg2), key
+        return self._beam_tab
+
+    def encode_beam(self, x: torch.Tensor, beam: int, chunk_rows: Optional[int] = None,
+                    check: Optional[bool] = None) -> Beam:
+        """Beam-search encode: ``beam`` partial paths per row, each scored by its original-space
+        reconstruction error, slot 0 always the greedy path (``paths[:, 0] == encode(x)``), the answer the slot with
+        the smallest finite error (lowest slot on ties), so never worse than greedy.  1 <= beam <= ops.TOPK_MAX.
+        Domain: the fused encoders (``self.fused``: one dimension group, no weights, L in {1, 3}) with
+        ``residual_global_id=True``; anything else raises ValueError.  f16 / bf16 rows stay 16-bit.  A row with a
+        non-finite value gets ids -1 and NaN errors; a row without a live path (penalty groups only) raises the
+        KeyError ``encode`` raises.  Rows are processed in chunks of ``chunk_rows`` (default ``2**21 // beam``, so a
+        chunk holds at most 2^21 items and its temporaries, about ``items * (12 * beam + 48)`` bytes, stay under
+        300 MB at beam 8).  ``check`` as in ``encode``."""
+        if check is None:
+            check = not torch.cuda.is_current_stream_capturing()
+        beam = int(beam)
+        if not 1 <= beam <= ops.TOPK_MAX:
+            raise ValueError(f"encode_beam: beam = {beam} (1..{ops.TOPK_MAX})")
+        if x.dim() != 2 or x.shape[1] != self.dim:
+            raise ValueError(f"Input dimension {x.shape[-1]} does not match config embedding_dim {self.dim}")
+        if not self.sem.residual_global_id:
+            raise ValueError("encode_beam: with residual_global_id=False the residual subtracts a centre other than "
+                             "the one assigned (the reference's predict quirk): a path has no reconstruction error")
+        if self.L == 2:
+            raise IndexError("list index out of range")  # as encode: the reference has no two-level form
+        if not self.fused or (self.L == 3 and self._last_raw is None):
+            raise ValueError("encode_beam: fused encoders only (one dimension group, no weights, one or three levels "
+                             "with the match lookup)")
+        if x.dtype not in (torch.float16, torch.bfloat16):
+            x = x.float()
+        x = x.contiguous()
+        self.last_row_format = ops.ROW_FORMAT_NAMES[x.dtype]
+        n, dev, B, L = x.shape[0], x.device, beam, self.L
+        chunk = int(chunk_rows) if chunk_rows else max(1, (1 << 21) // B)
+        chunk = max(1, min(chunk, (2 ** 31 - 1) // B))
+        paths = torch.empty((n, B, L), dtype=torch.int32, device=dev)
+        perr = torch.empty((n, B), dtype=torch.float32, device=dev)
+        if n:
+            if self._tws is None:
+                self._tws = ops.TopKWorkspace(min(n, chunk), B, self.device)
+            if self._xws is None:
+                self._xws = ops.BeamWorkspace(min(n, chunk) * B, B, self.device)
+        for r0 in range(0, n, chunk):
+            self._beam_chunk(x[r0:r0 + chunk], B, paths[r0:r0 + chunk], perr[r0:r0 + chunk])
+        fin = torch.where(torch.isfinite(perr), perr, torch.full_like(perr, float("inf")))
+        best = fin.min(1, keepdim=True).values
+        slots = torch.arange(B, dtype=torch.int32, device=dev).expand(n, B)
+        slot = torch.where(fin == best, slots, torch.full_like(slots, B)).min(1).values  # the lowest slot wins ties
+        pick = slot.long()
+        ids = paths.gather(1, pick.view(n, 1, 1).expand(n, 1, L)).reshape(n, L)
+        rec = perr.gather(1, pick.view(n, 1)).reshape(n)
+        if self.has_penalty and n:
+            bad = torch.nonzero(torch.isinf(rec))
+            if bad.numel():  # no live path: the row's groups allow no centre (encode: _finish_last)
+                raise KeyError(int(bad[0, 0].item()))
+        if check:
+            self.check_errors()
+        return Beam(ids, rec, paths, perr, slot)
+
+    def _beam_chunk(self, x, B, paths, perr):
+        """One chunk of encode_beam: level 0 is rqsid_assign_topk with k = B and a merge with beam_in = 1; the
+        later levels expand the B items of every row under their own parents and merge B * B expansions."""
+        n, dev = x.shape[0], x.device
+        norm = self.sem.normalize_residual
+        cands, seg1, seg2 = self._beam_tables(dev)
+        c0 = self.pcs[0].centers
+        loc, glob, dist = ops.assign_topk(x, self.pcs[0], ops.single_segment(n, dev), self.raw_cands[0], B,
+                                          workspace=self._tws, check=False)
+        st = ops.beam_merge(n, 1, B, B, 0, loc, glob, dist, use_global=True, dead_key=self.need[0])
+        if self.L == 3:
+            items = n * B
+            mult, n_groups = self._last_mult(), self.n_groups
+            den1 = torch.empty(items, dtype=torch.float32, device=dev) if norm else None
+            b = self._bucket(st.key, self.need[0] + 1)
+            fr = ops.FusedResidual(1, norm, c0, seg1, den_out=den1)
+            exp = ops.beam_expand(x, B, self.pcs[1], b, cands[1], B, fused=fr, workspace=self._xws, check=False)
+            st = ops.beam_merge(n, B, B, B, 1, *exp, scale_in=st.scale, den=den1, path_in=st.path, use_global=False,
+                                key_mult=mult, dead_key=n_groups)
+            if (self.need[0] - 1) * mult + self.need[1] - 1 >= n_groups:  # as _last_level_buckets (one host sync)
+                gmax = int(st.key.max().item())
+                if gmax > n_groups:
+                    raise IndexError(f"index {gmax} is out of bounds for axis 0 with size {n_groups}")
+            den2 = torch.empty(items, dtype=torch.float32, device=dev) if norm else None
+            b = self._bucket(st.key, n_groups + 1)
+            fr = ops.FusedResidual(2, norm, c0, seg2[0], self.pcs[1].centers, seg2[1], den_in=st.den_next,
+                                   den_out=den2)
+            exp = ops.beam_expand(x, B, self.pcs[2], b, cands[2], B, fused=fr, workspace=self._xws, check=False)
+            st = ops.beam_merge(n, B, B, B, 2, *exp, scale_in=st.scale, den=den2, path_in=st.path,
+                                use_global=not self.sem.remap_last)
+        paths.copy_(st.path.view(n, B, self.L))
+        perr.copy_(st.rec.view(n, B))
 
     def _last_level_buckets(self, out, l, n, device):
         if self.sem.match_lookup:

@@ -907,6 +907,56 @@ class HierarchicalRQKMeans:
         ids, alt, dist = (t.cpu().numpy() for t in parts)
         return ids.astype(np.int64), alt.astype(np.int64), dist
 
+    def _encode_beam_shard(self, X: np.ndarray, beam: int):
+        """This rank's shard through ``RQEncoder.encode_beam`` (training-consistent semantics): device tensors
+        ``[ids i32 [n, L], recon_err f32 [n], greedy_recon_err f32 [n], slot i32 [n]]`` and the Comm (or None)."""
+        if not self.is_trained or not self.cluster_centers_list:
+            raise RuntimeError("Model not trained. Call train() first or load a trained model.")
+        if X.shape[1] != self.config.embedding_dim:
+            raise ValueError(f"Input dimension {X.shape[1]} does not match config embedding_dim "
+                             f"{self.config.embedding_dim}")
+        from .quant_report import shard_rows
+        x, comm = shard_rows(X, self.device, self.group)
+        enc = self._encoder(False)
+        if x.shape[0]:
+            bm = enc.encode_beam(x, beam)
+            parts = [bm.ids.contiguous(), bm.recon_err.contiguous(), bm.path_err[:, 0].contiguous(), bm.slot]
+        else:
+            enc.encode_beam(x, beam)  # (the refusals are the same on a rank without rows)
+            L = len(self.config.layer_clusters)
+            parts = [torch.zeros((0, L), dtype=torch.int32, device=self.device),
+                     torch.zeros(0, dtype=torch.float32, device=self.device),
+                     torch.zeros(0, dtype=torch.float32, device=self.device),
+                     torch.zeros(0, dtype=torch.int32, device=self.device)]
+        return parts, comm
+
+    def predict_beam(self, X: np.ndarray, beam: int):
+        """Beam-search IDs (``RQEncoder.encode_beam`` with the training-consistent semantics): numpy arrays
+        ``(ids int64 [N, L], recon_err f32 [N], greedy_recon_err f32 [N])``, the last being the error of
+        ``predict(X, reference_quirks=False)``'s path (``recon_err <= greedy_recon_err`` on every row).  Rows are
+        sharded and the results all-gathered as in ``predict_topk``."""
+        parts, comm = self._encode_beam_shard(X, beam)
+        if comm is not None:
+            parts = [comm.all_gather_rows(t) for t in parts[:3]]
+        ids, rec, greedy = (t.cpu().numpy() for t in parts[:3])
+        return ids.astype(np.int64), rec, greedy
+
+    def beam_report(self, X: np.ndarray, beam: int) -> Dict:
+        """What a beam of ``beam`` buys on the rows ``X``: ``rows``, ``beam``, ``changed_share`` (rows whose beam ids
+        differ from the greedy ids), ``greedy_mse`` and ``beam_mse`` (mean squared original-space reconstruction
+        error; fp64 sums, all-reduced over the ranks, so every rank returns the same dict)."""
+        parts, comm = self._encode_beam_shard(X, beam)
+        ids, rec, greedy, slot = parts  # a beam path other than greedy's comes from another slot
+        tot = torch.stack([torch.tensor(float(ids.shape[0]), dtype=torch.float64, device=self.device),
+                           (slot != 0).double().sum(), greedy.double().pow(2).sum(), rec.double().pow(2).sum()])
+        if comm is not None:
+            tot = comm.all_reduce(tot)
+        rows, ch, g2, b2 = tot.cpu().tolist()
+        if rows == 0:
+            raise ValueError("beam_report: no rows")
+        return {"rows": int(rows), "beam": int(beam), "changed_share": ch / rows, "greedy_mse": g2 / rows,
+                "beam_mse": b2 / rows}
+
     def assignment_margins(self, X: np.ndarray) -> Dict:
         """Per level, how far the second-nearest allowed centre is behind the chosen one for the training-consistent
         IDs (margin_report.py has the keys).  With a process group each rank takes its shard and every rank

@@ -403,6 +403,134 @@ def nearest_topk(x: torch.Tensor, pc: PreparedCenters, k: int, workspace: Option
     return assign_topk(x, pc, single_segment(n, x.device), cand, k, workspace=workspace, check=check)
 
 
+class BeamWorkspace:
+    """Header of rqsid_beam_expand, laid out as rqsid_assign_topk's: bytes [0, 4) the sticky error word (zeroed here
+    once, never by a call), bytes [4, 16) the three per-call counters (they count items)."""
+
+    def __init__(self, n_items: int, k: int, device):
+        self.bytes = int(lib().rqsid_beam_expand_workspace_bytes(n_items, k))
+        self.buf = torch.empty(self.bytes, dtype=torch.uint8, device=device)
+        self.buf[:16].zero_()
+        self.n_items, self.k = n_items, k
+
+    def error_word(self) -> torch.Tensor:
+        return self.buf[:4].view(torch.int32)
+
+    def counters(self) -> dict:
+        """The last call's counters (host sync): items ranked from their list, items that took the all-candidate
+        pass, non-finite items."""
+        a, b, c = self.buf[4:16].view(torch.int32).tolist()
+        return {"listed_rows": a, "all_candidate_rows": b, "nonfinite_rows": c}
+
+
+def beam_expand(x: torch.Tensor, beam: int, pc: PreparedCenters, buckets: Buckets, cand: Candidates, k: int,
+                fused: Optional[FusedResidual] = None, workspace: Optional[BeamWorkspace] = None,
+                check: Optional[bool] = None, out=None):
+    """``assign_topk`` over ``N * beam`` items, item ``i`` (hypothesis ``i % beam`` of row ``i // beam``) reading row
+    ``i // beam`` of ``x`` [N, D] (include/rqsid.h rqsid_beam_expand): ``(local, global, dist)`` [N * beam, k].
+    ``buckets`` group the ITEMS by their hypothesis's segment (dead items in one extra segment whose ``cand.count`` is
+    0); ``fused.den_in`` / ``fused.den_out`` are per item, and ``den_out`` is written at levels 1 and 2.  ``check``,
+    ``out`` as in ``assign_topk``."""
+    if check is None:
+        check = not torch.cuda.is_current_stream_capturing()
+    _require_device(x, pc.centers, cand.base, cand.count, cand.idx, cand.flags, cand.lid)
+    x_format = ROW_FORMATS.get(x.dtype)
+    if x_format is None:
+        raise ValueError(f"rqsid_beam_expand reads float32, float16 or bfloat16 rows, not {x.dtype}")
+    n, d = x.shape
+    if d != pc.centers.shape[1]:
+        raise ValueError(f"dimension mismatch: x has {d}, centres {pc.centers.shape[1]}")
+    k, beam = int(k), int(beam)
+    if not 1 <= k <= TOPK_MAX or not 1 <= beam <= TOPK_MAX:
+        raise ValueError(f"rqsid_beam_expand: k = {k}, beam = {beam} (1..{TOPK_MAX})")
+    items = n * beam
+    dev = x.device
+    if out is None:
+        out = (torch.empty((items, k), dtype=torch.int32, device=dev),
+               torch.empty((items, k), dtype=torch.int32, device=dev),
+               torch.empty((items, k), dtype=torch.float32, device=dev))
+    loc, glob, dist = out
+    _require_device(loc, glob, dist)
+    if min(loc.numel(), glob.numel(), dist.numel()) < items * k:
+        raise ValueError("rqsid_beam_expand: an output holds fewer than N * beam * k values")
+    if workspace is None:
+        workspace = BeamWorkspace(items, k, dev)
+    f = fused
+    if f is not None:
+        _require_device(f.ca, f.seg_ca, f.cb, f.seg_cb, f.den_in, f.den_out)
+        for t in (f.den_in, f.den_out):
+            if t is not None and t.numel() < items:
+                raise ValueError("rqsid_beam_expand: den_in / den_out are per item (N * beam values)")
+    _lib.check(lib().rqsid_beam_expand(
+        _ptr(x), x_format, items, beam, d, _ptr(buckets.row_index), buckets.n_segments, _ptr(buckets.seg_row_off),
+        _ptr(buckets.seg_tile_off), buckets.max_tiles, _ptr(pc.centers), _ptr(pc.meta), pc.k,
+        _ptr(cand.base), _ptr(cand.count), cand.count_max, _ptr(cand.idx), _ptr(cand.lid), _ptr(cand.flags),
+        0 if f is None else f.levels, 0 if f is None else int(f.normalize),
+        None if f is None else _ptr(f.ca), None if f is None else _ptr(f.seg_ca),
+        None if f is None else _ptr(f.cb), None if f is None else _ptr(f.seg_cb),
+        None if f is None else _ptr(f.den_in), None if f is None else _ptr(f.den_out),
+        k, _ptr(loc), _ptr(glob), _ptr(dist), _ptr(workspace.buf), workspace.bytes, _stream()), "rqsid_beam_expand")
+    if check:
+        check_error_words([workspace.error_word()], "rqsid_beam_expand", TOPK_WORD)
+    return loc, glob, dist
+
+
+@dataclass
+class BeamStep:
+    """What ``beam_merge`` writes, per output item ``row * beam_out + t`` (include/rqsid.h rqsid_beam_merge)."""
+    path: torch.Tensor      # i32 [N * beam_out, level + 1]; -1 in a dead slot
+    scale: torch.Tensor     # f32: S_l of the slot's parent
+    den_next: torch.Tensor  # f32: the parent's divisor (the next level's den_in)
+    rec: torch.Tensor       # f32: fl32(S_l d), +inf in a dead slot, NaN in a non-finite row
+    key: torch.Tensor       # i32: the next level's segment key (dead_key in a dead slot)
+    src: torch.Tensor       # i32: parent * k + place, -1 in a dead slot
+
+
+def beam_merge(n_rows: int, beam_in: int, k: int, beam_out: int, level: int, exp_local: torch.Tensor,
+               exp_global: torch.Tensor, exp_dist: torch.Tensor, scale_in: Optional[torch.Tensor] = None,
+               den: Optional[torch.Tensor] = None, path_in: Optional[torch.Tensor] = None, use_global: bool = False,
+               key_mult: int = 0, dead_key: int = 0, out: Optional[BeamStep] = None) -> BeamStep:
+    """Per row, the next beam out of the ``beam_in * k`` expansions (include/rqsid.h rqsid_beam_merge): slot 0 the
+    greedy continuation, the others by ascending (rec, parent, place).  A pure function of its inputs (no workspace,
+    no error word).  ``out``: a ``BeamStep`` of buffers to write into."""
+    _require_device(exp_local, exp_global, exp_dist, scale_in, den, path_in)
+    n_rows, beam_in, k, beam_out, level = int(n_rows), int(beam_in), int(k), int(beam_out), int(level)
+    n_in = n_rows * beam_in
+    for t, dt in ((exp_local, torch.int32), (exp_global, torch.int32), (exp_dist, torch.float32)):
+        if t.dtype != dt or t.numel() < n_in * k:
+            raise ValueError("rqsid_beam_merge: the expansions are int32 / int32 / float32 [N * beam_in, k]")
+    for t in (scale_in, den):
+        if t is not None and (t.dtype != torch.float32 or t.numel() < n_in):
+            raise ValueError("rqsid_beam_merge: scale_in / den are float32 [N * beam_in]")
+    if level >= 1 and (path_in is None or path_in.dtype != torch.int32 or path_in.numel() < n_in * level):
+        raise ValueError("rqsid_beam_merge: path_in is int32 [N * beam_in, level]")
+    dev = exp_dist.device
+    n_out = n_rows * max(beam_out, 0)
+    if out is None:
+        out = BeamStep(torch.empty((n_out, level + 1), dtype=torch.int32, device=dev),
+                       torch.empty(n_out, dtype=torch.float32, device=dev),
+                       torch.empty(n_out, dtype=torch.float32, device=dev),
+                       torch.empty(n_out, dtype=torch.float32, device=dev),
+                       torch.empty(n_out, dtype=torch.int32, device=dev),
+                       torch.empty(n_out, dtype=torch.int32, device=dev))
+    _require_device(out.path, out.scale, out.den_next, out.rec, out.key, out.src)
+    _lib.check(lib().rqsid_beam_merge(
+        n_rows, beam_in, k, beam_out, level, _ptr(exp_local), _ptr(exp_global), _ptr(exp_dist), _ptr(scale_in),
+        _ptr(den), _ptr(path_in), int(bool(use_global)), int(key_mult), int(dead_key), _ptr(out.path),
+        _ptr(out.scale), _ptr(out.den_next), _ptr(out.rec), _ptr(out.key), _ptr(out.src), _stream()),
+        "rqsid_beam_merge")
+    return out
+
+
+def with_dead_segment(cand: Candidates) -> Candidates:
+    """``cand`` plus one last segment without candidates and without the penalty flag: where ``beam_expand`` keeps
+    the dead items (every slot -1 / -1 / +inf)."""
+    dev = cand.base.device
+    z = torch.zeros(1, dtype=torch.int32, device=dev)
+    flags = None if cand.flags is None else torch.cat([cand.flags, torch.zeros(1, dtype=torch.uint8, device=dev)])
+    return Candidates(torch.cat([cand.base, z]), torch.cat([cand.count, z]), cand.count_max, cand.idx, flags, cand.lid)
+
+
 def _groups_tensor(group_dims: Sequence[int], device) -> torch.Tensor:
     return torch.tensor(list(group_dims), dtype=torch.int32, device=device)
 

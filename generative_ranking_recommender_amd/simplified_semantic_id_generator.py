@@ -302,6 +302,17 @@ class SimplifiedHierarchicalRQ:
         return (tk.ids.cpu().numpy().astype(np.int64), tk.local.cpu().numpy().astype(np.int64),
                 tk.dist.contiguous().cpu().numpy())
 
+    def predict_beam(self, X: np.ndarray, beam: int):
+        """Beam-search IDs of the trained codebooks (``RQEncoder.encode_beam``): numpy arrays ``(ids int64 [N, L],
+        recon_err f32 [N], greedy_recon_err f32 [N])``, the last being the error of the greedy path
+        (``recon_err <= greedy_recon_err`` on every row)."""
+        from .quant_report import shard_rows
+        enc = self._trained_encoder("predict_beam", X)
+        x, _ = shard_rows(X, self.device)
+        bm = enc.encode_beam(x, beam)
+        return (bm.ids.cpu().numpy().astype(np.int64), bm.recon_err.cpu().numpy(),
+                bm.path_err[:, 0].contiguous().cpu().numpy())
+
     def assignment_margins(self, X: np.ndarray) -> Dict:
         """Per level, how far the second-nearest allowed centre is behind the chosen one (margin_report.py has the
         keys)."""

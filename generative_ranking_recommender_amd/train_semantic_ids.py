@@ -31,8 +31,11 @@ class SemanticIDTrainer:
     """train_semantic_ids.py:35-365."""
 
     def __init__(self, config, use_test_config: bool = False, device=None, group=None,
-                 report_quantization: bool = False, report_margins: bool = False):
+                 report_quantization: bool = False, report_margins: bool = False, report_beam: int = 0):
         self.config = config
+        # opt-in (a beam width 1..8): also write beam_report.json (HierarchicalRQKMeans.beam_report of the training
+        # rows: what a beam-search encode of that width would change and gain); the IDs written stay greedy
+        self.report_beam = int(report_beam or 0)
         # opt-in: also write assignment_margin_report.json (HierarchicalRQKMeans.assignment_margins of the training
         # rows) next to the other side files
         self.report_margins = report_margins
@@ -95,6 +98,11 @@ class SemanticIDTrainer:
             if self.rank == 0:
                 rq_io.write_json(str(self.output_dir / "assignment_margin_report.json"), margins)
             result["assignment_margin_report"] = margins
+        if self.report_beam:
+            beam = model.beam_report(vectors, self.report_beam)  # every rank takes part, as above
+            if self.rank == 0:
+                rq_io.write_json(str(self.output_dir / "beam_report.json"), beam)
+            result["beam_report"] = beam
         return result
 
     def _generate_semantic_ids(self, song_ids: list, train_result: Dict) -> Dict:

@@ -210,6 +210,60 @@ int rqsid_assign_topk(const void* x, int32_t x_format, int64_t n_rows, int32_t d
                       int32_t k, int32_t* out_local, int32_t* out_global, float* out_dist,
                       void* workspace, int64_t workspace_bytes, void* stream);
 
+/* Beam-search encode, step 1: rqsid_assign_topk over n_items = n_rows * beam items, item-major
+ * (item = row * beam + h is hypothesis h of a row).  Every argument means what it means for rqsid_assign_topk (the
+ * same kernel, instantiated for items), with three differences:
+ *  - item i reads row i / beam of x: x keeps n_items / beam rows in any x_format, and no residual or replicated
+ *    matrix is written.  row_index, the segments and tiles (rqsid_bucket over the items' keys), every output
+ *    ([n_items][k]) and the counters count items;
+ *  - den_in is indexed by item;
+ *  - den_out (when given and res_normalize) receives the level's own divisor fl32(sqrt(fp64 sum)) + 1e-8f at
+ *    res_levels 1 AND 2, indexed by item.
+ * A dead hypothesis is an item like any other: the caller buckets it into one extra segment with cand_count = 0
+ * (every slot -1 / -1 / +inf) whose seg_ca / seg_cb entries name row 0.
+ * n_items % beam == 0 and 1 <= beam <= RQSID_TOPK_MAX; the other limits, the refusals before any HIP call, the
+ * workspace header (sticky error word, three counters) are those of rqsid_assign_topk.  With beam = 1 the outputs
+ * are byte-identical to rqsid_assign_topk on the same tables. */
+int64_t rqsid_beam_expand_workspace_bytes(int64_t n_items, int32_t k);
+int rqsid_beam_expand(const void* x, int32_t x_format, int64_t n_items, int32_t beam, int32_t dim,
+                      const int32_t* row_index,
+                      int32_t n_segments, const int32_t* seg_row_off, const int32_t* seg_tile_off, int64_t max_tiles,
+                      const float* centers, const float* c_meta, int32_t n_centers,
+                      const int32_t* cand_base, const int32_t* cand_count, int32_t cand_count_max,
+                      const int32_t* cand_idx, const int32_t* cand_lid, const uint8_t* seg_flags,
+                      int32_t res_levels, int32_t res_normalize,
+                      const float* ca, const int32_t* seg_ca, const float* cb, const int32_t* seg_cb,
+                      const float* den_in, float* den_out,
+                      int32_t k, int32_t* out_local, int32_t* out_global, float* out_dist,
+                      void* workspace, int64_t workspace_bytes, void* stream);
+
+/* Beam-search encode, step 2: per row, the next beam out of the beam_in * k expansions of its beam_in hypotheses
+ * (beam_in = 1 at level 0, where the expansions are rqsid_assign_topk's).  Inputs, by input item = row * beam_in + h:
+ * exp_local / exp_global / exp_dist [n_rows * beam_in][k] (rqsid_beam_expand's outputs); scale_in = S_{l-1} and den =
+ * the level's divisor den_l (either may be NULL, meaning 1); path_in [n_rows * beam_in][level] (NULL at level 0).
+ * use_global != 0 takes exp_global as the level's id, else exp_local.
+ * An expansion (h, place) with ids >= 0 scores rec = fl32(S_l d), S_l = fl32(scale_in[h] den[h]), d its exp_dist:
+ * the original-space error of the path up to this level.  It is live when rec is finite.  Output slot 0 is always
+ * (h = 0, place = 0), the greedy continuation (dead if that expansion is not live); slots 1 .. beam_out - 1 are the
+ * other live expansions in ascending (rec, h, place) order; slots nothing fills are dead.  Outputs, by output item
+ * row * beam_out + t: path_out [level + 1] (the parent's prefix, then the id); scale_out = S_l of the parent;
+ * den_next = den of the parent (the next level's den_in); rec_out; key_out = (level >= 1 ? path_in[h][level - 1] *
+ * key_mult : 0) + id (the next level's segment key); src_out = h * k + place.  A dead slot: ids -1, scale_out 1,
+ * den_next 1, rec_out +inf, key_out = dead_key, src_out -1.  A row with a NaN exp_dist or a NaN scale_in in any input
+ * item (a non-finite row): every slot dead with rec_out = scale_out = NaN, so the NaN reaches the last level.  The
+ * den of an item without a live expansion never reaches an output (rqsid_beam_expand leaves it unwritten for the
+ * items of a penalty segment).
+ * One wave per row, no atomics, no device-counter-driven writes: a pure function of its inputs, bit-reproducible,
+ * stream-ordered, graph-capturable.  RQSID_E_ARG before any launch: beam_in, k, beam_out outside 1 .. RQSID_TOPK_MAX,
+ * beam_out > beam_in * k, level outside 0 .. 7, more than 2^31 - 1 items, a null required pointer (every output, the
+ * expansions, path_in at level >= 1).  n_rows == 0 succeeds without touching anything. */
+int rqsid_beam_merge(int64_t n_rows, int32_t beam_in, int32_t k, int32_t beam_out, int32_t level,
+                     const int32_t* exp_local, const int32_t* exp_global, const float* exp_dist,
+                     const float* scale_in, const float* den, const int32_t* path_in,
+                     int32_t use_global, int32_t key_mult, int32_t dead_key,
+                     int32_t* path_out, float* scale_out, float* den_next, float* rec_out,
+                     int32_t* key_out, int32_t* src_out, void* stream);
+
 /* Residual r = x - c[center_id[row]]; with normalize != 0 each dimension group
  * g is divided by (||r_g|| + 1e-8).  Replaces _compute_residuals_with_centers
  * (hierarchical_rq_kmeans.py:1088-1128) and the plain residuals of
