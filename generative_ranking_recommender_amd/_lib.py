@@ -24,7 +24,7 @@ SRCS = [PKG / "csrc" / "rqsid.hip", PKG / "csrc" / "assign.hip", PKG / "csrc" / 
         PKG / "csrc" / "auction_seg.hip", PKG / "csrc" / "quant_error.hip", PKG / "csrc" / "assign_topk.hip",
         PKG / "csrc" / "beam.hip"]
 DEPS = SRCS + [PKG / "csrc" / "internal.h", PKG / "csrc" / "assign_common.h", PKG / "csrc" / "assign_plan.h",
-               PKG / "csrc" / "topk_kernel.h"]
+               PKG / "csrc" / "topk_kernel.h", PKG / "csrc" / "exact_row.h"]
 HEADER = REPO / "include" / "rqsid.h"
 # host-only I/O library (CSV reader): plain g++, no GPU code
 IO_LIB_PATH = PKG / "librqsid_io.so"

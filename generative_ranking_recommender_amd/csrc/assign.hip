@@ -28,6 +28,7 @@
 // The residual centres are per-SEGMENT constants (a level's segment determines the parent IDs), so
 // they are staged once per tile in LDS.
 #include "assign_common.h"
+#include "exact_row.h"
 
 namespace rqsid {
 namespace {
@@ -791,174 +792,18 @@ __global__ __launch_bounds__(256, screen_min_blocks(NT, S, T3, 1)) void assign_s
 // ---------------------------------------------------------------------------
 // exact re-score
 // ---------------------------------------------------------------------------
-// One wave per listed row.  The row's vector is rebuilt with the reference's fp32 operation sequence
-// (x - ca, / n1, - cb, / n2 with n = fl(sqrt(sum^2)) + 1e-8) and held in registers, lanes over dims;
-// candidates are scored 8 at a time (coalesced 2 KB centre-row reads, fp64 sums of (v - c)^2, one
-// batched cross-lane reduction), so explicit lists cost one batch and "every candidate" / penalty rows
-// cost ceil(n/8) batches.  The winner is the lexicographic minimum (distance, local index).
-constexpr int kRescoreMaxV = kMaxDim / 256;  // float4 per lane
-constexpr int kBatch = 8;
-
-template <int RL, bool NORM, int XF>
-__device__ __forceinline__ void rescore_rows(const AssignParams& p) {
-  const int lane = threadIdx.x & 63;
-  const int wid = blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int nw = gridDim.x * 4;
-  const int64_t nitems_raw = *p.work_count;
-  const int64_t nitems = nitems_raw < p.work_cap ? nitems_raw : p.work_cap;
-  const int nv = p.dim / 4;
-  // Items are strided over every wave of the grid: the "every candidate" rows cluster in a few
-  // segments (duplicated centres), and striding spreads them evenly over the waves.
-  for (int64_t it = wid; it < nitems; it += nw) {
-    const WorkItem w = p.work[p.work_idx ? p.work_idx[it] : it];
-    const float* car = RL >= 1 ? p.ca + (int64_t)seg_row(p.seg_ca, w.seg) * p.dim : nullptr;
-    const float* cbr = RL >= 2 ? p.cb + (int64_t)seg_row(p.seg_cb, w.seg) * p.dim : nullptr;
-    const bool screened = w.n >= 1 || w.n == -1;  // the screen wrote den_out for these rows
-    float4 v[kRescoreMaxV];
-    double ss = 0.0;
-#pragma unroll
-    for (int m = 0; m < kRescoreMaxV; ++m) {
-      const int i = lane + 64 * m;
-      if (i < nv) {
-        float4 a = load_row4<XF>(p.x, w.row, p.dim, i);
-        if (RL >= 1) {
-          const float4 c = reinterpret_cast<const float4*>(car)[i];
-          a = make_float4(a.x - c.x, a.y - c.y, a.z - c.z, a.w - c.w);
-        }
-        if (RL >= 2) {
-          if (NORM) {
-            const float d1 = p.den_in[w.row];
-            a = make_float4(a.x / d1, a.y / d1, a.z / d1, a.w / d1);
-          }
-          const float4 c = reinterpret_cast<const float4*>(cbr)[i];
-          a = make_float4(a.x - c.x, a.y - c.y, a.z - c.z, a.w - c.w);
-        }
-        v[m] = a;
-        ss += (double)a.x * a.x + (double)a.y * a.y + (double)a.z * a.z + (double)a.w * a.w;
-      } else {
-        v[m] = make_float4(0.f, 0.f, 0.f, 0.f);
-      }
-    }
-    if (NORM && RL >= 1) {
-      float den;
-      if (RL == 1 && p.den_out && screened) den = p.den_out[w.row];
-      else den = (float)sqrt(wave_sum(ss)) + 1e-8f;
-      if (RL == 1 && p.den_out && !screened && lane == 0) p.den_out[w.row] = den;
-#pragma unroll
-      for (int m = 0; m < kRescoreMaxV; ++m)
-        v[m] = make_float4(v[m].x / den, v[m].y / den, v[m].z / den, v[m].w / den);
-    }
-    const bool penalty = w.n == -2;
-    const bool listed = w.n >= 1;
-    const int base = p.cand_base[w.seg];
-    const int n = listed ? w.n : (penalty ? p.n_centers : (w.n == -1 ? p.cand_count[w.seg] : 0));
-    double best = INFINITY;  // penalty rows compare fl32(sqrt(fl32(d^2))) + 10000 in fp32, as the reference
-    int bj = INT_MAX;
-    for (int j0 = 0; j0 < n; j0 += kBatch) {
-      double acc[kBatch];
-      int loc[kBatch];
-#pragma unroll
-      for (int jj = 0; jj < kBatch; ++jj) {
-        const int j = j0 + jj;
-        acc[jj] = 0.0;
-        loc[jj] = j < n ? (listed ? (int)w.cand[jj] : j) : INT_MAX;
-        if (j < n) {
-          const int g = penalty ? loc[jj] : cand_global(p, base, loc[jj]);
-          const float4* cr = reinterpret_cast<const float4*>(p.centers + (int64_t)g * p.dim);
-#pragma unroll
-          for (int m = 0; m < kRescoreMaxV; ++m) {
-            const int i = lane + 64 * m;
-            if (i < nv) {
-              const float4 c = cr[i];
-              const double d0 = (double)v[m].x - c.x, d1 = (double)v[m].y - c.y, d2 = (double)v[m].z - c.z,
-                           d3 = (double)v[m].w - c.w;
-              acc[jj] += d0 * d0 + d1 * d1 + d2 * d2 + d3 * d3;
-            }
-          }
-        }
-      }
-      // halving cross-lane reduction: 4 + 2 + 1 exchanges leave lane l holding the wave total of
-      // candidate jj(l) = 4*(l>>5) + 2*((l>>4)&1) + ((l>>3)&1) summed over its 8-lane group; 3 more
-      // exchanges finish it.  10 shuffles for 8 sums instead of 48.
-      double r4[4], r2[2], r1;
-      const bool b5 = lane & 32, b4 = lane & 16, b3 = lane & 8;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const double send = b5 ? acc[j] : acc[j + 4];
-        const double keep = b5 ? acc[j + 4] : acc[j];
-        r4[j] = keep + __shfl_xor(send, 32);
-      }
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const double send = b4 ? r4[j] : r4[j + 2];
-        const double keep = b4 ? r4[j + 2] : r4[j];
-        r2[j] = keep + __shfl_xor(send, 16);
-      }
-      {
-        const double send = b3 ? r2[0] : r2[1];
-        const double keep = b3 ? r2[1] : r2[0];
-        r1 = keep + __shfl_xor(send, 8);
-      }
-      r1 += __shfl_xor(r1, 4);
-      r1 += __shfl_xor(r1, 2);
-      r1 += __shfl_xor(r1, 1);
-      const int my_jj = 4 * (lane >> 5) + 2 * ((lane >> 4) & 1) + ((lane >> 3) & 1);
-      int my_loc = INT_MAX;
-#pragma unroll
-      for (int jj = 0; jj < kBatch; ++jj) my_loc = my_jj == jj ? loc[jj] : my_loc;
-      double key = r1;
-      if (penalty) key = (double)((float)sqrt((double)(float)key) + 10000.0f);
-      // lexicographic (distance, index) minimum over the batch (lanes) and the running best; a NaN
-      // distance never displaces a real one
-#pragma unroll
-      for (int o = 8; o < 64; o <<= 1) {
-        const double ok = __shfl_xor(key, o);
-        const int ol = __shfl_xor(my_loc, o);
-        const bool kn = key != key, okn = ok != ok;
-        const bool take = ol != INT_MAX && (my_loc == INT_MAX || (!okn && (kn || ok < key || (ok == key && ol < my_loc))));
-        key = take ? ok : key;
-        my_loc = take ? ol : my_loc;
-      }
-      {
-        const bool kn = key != key, bn = best != best;
-        const bool take = my_loc != INT_MAX &&
-                          (bj == INT_MAX || (!kn && (bn || key < best || (key == best && my_loc < bj))));
-        if (take) {
-          best = key;
-          bj = my_loc;
-        }
-      }
-    }
-    if (lane == 0) {
-      const bool found = bj != INT_MAX;
-      p.out_local[w.row] = found && !penalty ? cand_local(p, base, bj) : -1;
-      p.out_global[w.row] = found ? (penalty ? bj : cand_global(p, base, bj)) : -1;
-    }
-  }
-}
-// (the re-score kernels, like the screen: one body, an fp32-row build under the name the profiles key on and
-// 16-bit-row builds that widen the row as they load it, load_row4)
-template <int RL, bool NORM>
-__global__ __launch_bounds__(256) void assign_rescore_kernel(AssignParams p) {
-  rescore_rows<RL, NORM, RQSID_X_F32>(p);
-}
-template <int XF, int RL, bool NORM>
-__global__ __launch_bounds__(256) void assign_rescore_x16_kernel(AssignParams p) {
-  rescore_rows<RL, NORM, XF>(p);
-}
-
-// Two listed rows per wave (rows of at most kHalfDim dims): lanes 32 hh .. 32 hh + 31 re-score item
-// 2 wid + hh of the pass with 4 float4 of the row per lane; the same arithmetic, candidate batches and
-// (distance, index) rule as assign_rescore_kernel, with every reduction kept inside the half.  The
-// re-score is bound by its dependent-load chain (item -> row, residual rows -> candidate rows), not by
-// bytes, and a wave now carries two chains at the same register count.
+// W lanes per listed row, the arithmetic that of exact_row.h: the row's vector rebuilt and held in registers,
+// lanes over dims; candidates scored kBatch at a time (coalesced 2 KB centre-row reads, one batched
+// cross-lane reduction), so explicit lists cost one batch and "every candidate" / penalty rows cost
+// ceil(n/8) batches.  The winner is the lexicographic minimum (distance, local index).
+//
+// W = 64 (assign_rescore_kernel): one wave per row, rows of any width up to kMaxDim, mode 0.
+// W = 32 (assign_rescore_half_kernel): two listed rows per wave (rows of at most kHalfDim dims): lanes
+// 32 hh .. 32 hh + 31 re-score item 2 wid + hh of the pass with 4 float4 of the row per lane, every
+// reduction kept inside the half.  The re-score is bound by its dependent-load chain (item -> row, residual
+// rows -> candidate rows), not by bytes, and a wave now carries two chains at the same register count.
 constexpr int kHalfDim = 512;
 static_assert(kHalfDim == kPlanHalfDim, "assign_plan.h constants");
-__device__ __forceinline__ double half_sum(double v) {
-#pragma unroll
-  for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
 
 // mode 0: every work item; after the fp32 re-screen the items it left "every candidate" (n = -1: a true
 // cluster of > kMaxList candidates, e.g. near-equal distances of a zero residual row) go to their own pass
@@ -971,16 +816,19 @@ constexpr int kOvfSlot = 56;  // workspace header int: overflow item count
 // checked against its slot's capacity; a write that would fall outside is dropped and its bit raised, so
 // a wrong count can only produce a reported error, never a store outside the workspace.
 // (kErrSlot and its bits: assign_common.h)
-template <int RL, bool NORM, int XF>
-__device__ __forceinline__ void rescore_half_rows(const AssignParams& p, const int32_t* __restrict__ ovf_list, int mode) {
-  constexpr int kV = kHalfDim / 128;  // float4 per lane
-  const int lane = threadIdx.x & 63, hl = lane & 31, hh = lane >> 5;
+template <int RL, bool NORM, int XF, int W>
+__device__ __forceinline__ void rescore_rows(const AssignParams& p, const int32_t* __restrict__ ovf_list, int mode) {
+  constexpr int G = 64 / W;                                     // items per wave
+  constexpr int kV = (W == 64 ? kMaxDim : kHalfDim) / (4 * W);  // float4 per lane
+  const int lane = threadIdx.x & 63, gl = lane & (W - 1), hh = lane / W;
   const int wid = blockIdx.x * 4 + (threadIdx.x >> 6);
   const int nw = gridDim.x * 4;
   const int64_t nitems_raw = mode == 2 ? p.work_count[kOvfSlot] : *p.work_count;
   const int64_t nitems = nitems_raw < p.work_cap ? nitems_raw : p.work_cap;
   const int nv = p.dim / 4;
-  for (int64_t it0 = 2 * (int64_t)wid; it0 < nitems; it0 += 2 * (int64_t)nw) {
+  // Items are strided over every wave of the grid: the "every candidate" rows cluster in a few
+  // segments (duplicated centres), and striding spreads them evenly over the waves.
+  for (int64_t it0 = G * (int64_t)wid; it0 < nitems; it0 += G * (int64_t)nw) {
     const int64_t it = it0 + hh < nitems ? it0 + hh : it0;
     const WorkItem w = p.work[mode == 2 ? ovf_list[it] : (p.work_idx ? p.work_idx[it] : it)];
     // an idle half (past the end, or an item of the other pass) repeats the work and writes nothing
@@ -989,133 +837,66 @@ __device__ __forceinline__ void rescore_half_rows(const AssignParams& p, const i
     const float* cbr = RL >= 2 ? p.cb + (int64_t)seg_row(p.seg_cb, w.seg) * p.dim : nullptr;
     const bool screened = w.n >= 1 || w.n == -1;  // the screen wrote den_out for these rows
     float4 v[kV];
-    double ss = 0.0;
-#pragma unroll
-    for (int m = 0; m < kV; ++m) {
-      const int i = hl + 32 * m;
-      if (i < nv) {
-        float4 a = load_row4<XF>(p.x, w.row, p.dim, i);
-        if (RL >= 1) {
-          const float4 c = reinterpret_cast<const float4*>(car)[i];
-          a = make_float4(a.x - c.x, a.y - c.y, a.z - c.z, a.w - c.w);
-        }
-        if (RL >= 2) {
-          if (NORM) {
-            const float d1 = p.den_in[w.row];
-            a = make_float4(a.x / d1, a.y / d1, a.z / d1, a.w / d1);
-          }
-          const float4 c = reinterpret_cast<const float4*>(cbr)[i];
-          a = make_float4(a.x - c.x, a.y - c.y, a.z - c.z, a.w - c.w);
-        }
-        v[m] = a;
-        ss += (double)a.x * a.x + (double)a.y * a.y + (double)a.z * a.z + (double)a.w * a.w;
-      } else {
-        v[m] = make_float4(0.f, 0.f, 0.f, 0.f);
-      }
-    }
+    const double ss = build_row<RL, NORM, XF, W>(p.x, w.row, p.dim, car, cbr, p.den_in, gl, v);
     if (NORM && RL >= 1) {
       float den;
       if (RL == 1 && p.den_out && screened) den = p.den_out[w.row];
-      else den = (float)sqrt(half_sum(ss)) + 1e-8f;
-      if (RL == 1 && p.den_out && !screened && hl == 0 && active) p.den_out[w.row] = den;
+      else den = chain_divisor<W>(ss);
+      if (RL == 1 && p.den_out && !screened && gl == 0 && active) p.den_out[w.row] = den;
 #pragma unroll
-      for (int m = 0; m < kV; ++m)
-        v[m] = make_float4(v[m].x / den, v[m].y / den, v[m].z / den, v[m].w / den);
+      for (int m = 0; m < kV; ++m) v[m] = div4(v[m], den);
     }
     const bool penalty = w.n == -2;
     const bool listed = w.n >= 1;
     const int base = p.cand_base[w.seg];
     const int n = !active ? 0 : listed ? w.n : (penalty ? p.n_centers : (w.n == -1 ? p.cand_count[w.seg] : 0));
-    const int nmax = max(n, __shfl_xor(n, 32));  // both halves run the same batches
-    double best = INFINITY;
+    const int nmax = G == 2 ? max(n, __shfl_xor(n, 32)) : n;  // both halves run the same batches
+    double best = INFINITY;  // penalty rows compare fl32(sqrt(fl32(d^2))) + 10000 in fp32, as the reference
     int bj = INT_MAX;
     for (int j0 = 0; j0 < nmax; j0 += kBatch) {
-      double acc[kBatch];
-      int loc[kBatch];
-#pragma unroll
-      for (int jj = 0; jj < kBatch; ++jj) {
-        const int j = j0 + jj;
-        acc[jj] = 0.0;
-        loc[jj] = j < n ? (listed ? (int)w.cand[jj] : j) : INT_MAX;
-        if (j < n) {
-          const int g = penalty ? loc[jj] : cand_global(p, base, loc[jj]);
-          const float4* cr = reinterpret_cast<const float4*>(p.centers + (int64_t)g * p.dim);
-#pragma unroll
-          for (int m = 0; m < kV; ++m) {
-            const int i = hl + 32 * m;
-            if (i < nv) {
-              const float4 c = cr[i];
-              const double d0 = (double)v[m].x - c.x, d1 = (double)v[m].y - c.y, d2 = (double)v[m].z - c.z,
-                           d3 = (double)v[m].w - c.w;
-              acc[jj] += d0 * d0 + d1 * d1 + d2 * d2 + d3 * d3;
-            }
-          }
-        }
-      }
-      // halving reduction inside the half: 4 + 2 + 1 exchanges leave lane hl holding candidate
-      // jj(hl) = 4*((hl>>4)&1) + 2*((hl>>3)&1) + ((hl>>2)&1) summed over its 4-lane group; 2 more finish it
-      double r4[4], r2[2], r1;
-      const bool b4 = hl & 16, b3 = hl & 8, b2 = hl & 4;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const double send = b4 ? acc[j] : acc[j + 4];
-        const double keep = b4 ? acc[j + 4] : acc[j];
-        r4[j] = keep + __shfl_xor(send, 16);
-      }
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const double send = b3 ? r4[j] : r4[j + 2];
-        const double keep = b3 ? r4[j + 2] : r4[j];
-        r2[j] = keep + __shfl_xor(send, 8);
-      }
-      {
-        const double send = b2 ? r2[0] : r2[1];
-        const double keep = b2 ? r2[1] : r2[0];
-        r1 = keep + __shfl_xor(send, 4);
-      }
-      r1 += __shfl_xor(r1, 2);
-      r1 += __shfl_xor(r1, 1);
-      const int my_jj = 4 * ((hl >> 4) & 1) + 2 * ((hl >> 3) & 1) + ((hl >> 2) & 1);
+      // list position of the batch's candidate jj (a list has at most kBatch entries: one batch)
+      auto loc = [&](int jj) { return listed ? (int)w.cand[jj] : j0 + jj; };
+      double key = batch_dist2<W, double>(v, gl, nv, j0, n, [&](int jj) {
+        const int g = penalty ? loc(jj) : cand_global(p, base, loc(jj));
+        return reinterpret_cast<const float4*>(p.centers + (int64_t)g * p.dim);
+      });
+      const int my_jj = batch_slot<W>(gl);
       int my_loc = INT_MAX;
 #pragma unroll
-      for (int jj = 0; jj < kBatch; ++jj) my_loc = my_jj == jj ? loc[jj] : my_loc;
-      double key = r1;
+      for (int jj = 0; jj < kBatch; ++jj) my_loc = my_jj == jj ? (j0 + jj < n ? loc(jj) : INT_MAX) : my_loc;
       if (penalty) key = (double)((float)sqrt((double)(float)key) + 10000.0f);
-#pragma unroll
-      for (int o = 4; o < 32; o <<= 1) {
-        const double ok = __shfl_xor(key, o);
-        const int ol = __shfl_xor(my_loc, o);
-        const bool kn = key != key, okn = ok != ok;
-        const bool take = ol != INT_MAX && (my_loc == INT_MAX || (!okn && (kn || ok < key || (ok == key && ol < my_loc))));
-        key = take ? ok : key;
-        my_loc = take ? ol : my_loc;
-      }
-      {
-        const bool kn = key != key, bn = best != best;
-        const bool take = my_loc != INT_MAX &&
-                          (bj == INT_MAX || (!kn && (bn || key < best || (key == best && my_loc < bj))));
-        if (take) {
-          best = key;
-          bj = my_loc;
-        }
+      group_min<W>(key, my_loc);  // over the batch, then against the running best
+      if (takes(key, my_loc, best, bj)) {
+        best = key;
+        bj = my_loc;
       }
     }
-    if (hl == 0 && active) {
+    if (gl == 0 && active) {
       const bool found = bj != INT_MAX;
       p.out_local[w.row] = found && !penalty ? cand_local(p, base, bj) : -1;
       p.out_global[w.row] = found ? (penalty ? bj : cand_global(p, base, bj)) : -1;
     }
   }
 }
+// (the re-score kernels, like the screen: one body, an fp32-row build under the name the profiles key on and
+// 16-bit-row builds that widen the row as they load it, load_row4)
+template <int RL, bool NORM>
+__global__ __launch_bounds__(256) void assign_rescore_kernel(AssignParams p) {
+  rescore_rows<RL, NORM, RQSID_X_F32, 64>(p, nullptr, 0);
+}
+template <int XF, int RL, bool NORM>
+__global__ __launch_bounds__(256) void assign_rescore_x16_kernel(AssignParams p) {
+  rescore_rows<RL, NORM, XF, 64>(p, nullptr, 0);
+}
 template <int RL, bool NORM>
 __global__ __launch_bounds__(256) void assign_rescore_half_kernel(AssignParams p, const int32_t* __restrict__ ovf_list,
                                                                   int mode) {
-  rescore_half_rows<RL, NORM, RQSID_X_F32>(p, ovf_list, mode);
+  rescore_rows<RL, NORM, RQSID_X_F32, 32>(p, ovf_list, mode);
 }
 template <int XF, int RL, bool NORM>
 __global__ __launch_bounds__(256) void assign_rescore_half_x16_kernel(AssignParams p, const int32_t* __restrict__ ovf_list,
                                                                       int mode) {
-  rescore_half_rows<RL, NORM, XF>(p, ovf_list, mode);
+  rescore_rows<RL, NORM, XF, 32>(p, ovf_list, mode);
 }
 
 // ---------------------------------------------------------------------------
@@ -1166,38 +947,14 @@ __device__ __forceinline__ void rescreen_rows(const AssignParams& p, const int32
     WorkItem w = p.work[idx];
     const float* car = RL >= 1 ? p.ca + (int64_t)seg_row(p.seg_ca, w.seg) * p.dim : nullptr;
     const float* cbr = RL >= 2 ? p.cb + (int64_t)seg_row(p.seg_cb, w.seg) * p.dim : nullptr;
-    // the row as the re-score rebuilds it (the reference's fp32 operation sequence)
+    // the row as the re-score rebuilds it
     float4 v[kV];
-    double ss = 0.0;
-#pragma unroll
-    for (int m = 0; m < kV; ++m) {
-      const int i = hl + 32 * m;
-      if (i < nv) {
-        float4 a = load_row4<XF>(p.x, w.row, p.dim, i);
-        if (RL >= 1) {
-          const float4 c = reinterpret_cast<const float4*>(car)[i];
-          a = make_float4(a.x - c.x, a.y - c.y, a.z - c.z, a.w - c.w);
-        }
-        if (RL >= 2) {
-          if (NORM) {
-            const float d1 = p.den_in[w.row];
-            a = make_float4(a.x / d1, a.y / d1, a.z / d1, a.w / d1);
-          }
-          const float4 c = reinterpret_cast<const float4*>(cbr)[i];
-          a = make_float4(a.x - c.x, a.y - c.y, a.z - c.z, a.w - c.w);
-        }
-        v[m] = a;
-        ss += (double)a.x * a.x + (double)a.y * a.y + (double)a.z * a.z + (double)a.w * a.w;
-      } else {
-        v[m] = make_float4(0.f, 0.f, 0.f, 0.f);
-      }
-    }
+    const double ss = build_row<RL, NORM, XF, 32>(p.x, w.row, p.dim, car, cbr, p.den_in, hl, v);
     if (NORM && RL >= 1) {
       // the screen wrote den_out for every listed row at RL = 1; level 2 recomputes its own divisor
-      const float den = (RL == 1 && p.den_out) ? p.den_out[w.row] : (float)sqrt(half_sum(ss)) + 1e-8f;
+      const float den = (RL == 1 && p.den_out) ? p.den_out[w.row] : chain_divisor<32>(ss);
 #pragma unroll
-      for (int m = 0; m < kV; ++m)
-        v[m] = make_float4(v[m].x / den, v[m].y / den, v[m].z / den, v[m].w / den);
+      for (int m = 0; m < kV; ++m) v[m] = div4(v[m], den);
     }
     const int base = p.cand_base[w.seg];
     const int n = p.cand_count[w.seg];
@@ -1213,36 +970,11 @@ __device__ __forceinline__ void rescreen_rows(const AssignParams& p, const int32
       llb[k] = INFINITY;
     }
     for (int j0 = 0; j0 < nmax; j0 += kBatch) {
-      float acc[kBatch];
-#pragma unroll
-      for (int jj = 0; jj < kBatch; ++jj) {
-        const int j = j0 + jj;
-        acc[jj] = 0.f;
-        if (j < n) {
-          const float4* cr = reinterpret_cast<const float4*>(p.centers + (int64_t)cand_global(p, base, j) * p.dim);
-#pragma unroll
-          for (int m = 0; m < kV; ++m) {
-            const int i = hl + 32 * m;
-            if (i < nv) {
-              const float4 c = cr[i];
-              const float d0 = v[m].x - c.x, d1 = v[m].y - c.y, d2 = v[m].z - c.z, d3 = v[m].w - c.w;
-              acc[jj] = fmaf(d0, d0, fmaf(d1, d1, fmaf(d2, d2, fmaf(d3, d3, acc[jj]))));
-            }
-          }
-        }
-      }
-      // the re-score's halving reduction inside the half (fp32): lane hl ends with candidate
-      // jj(hl) = 4*((hl>>4)&1) + 2*((hl>>3)&1) + ((hl>>2)&1) summed over the half
-      float r4[4], r2[2], r1;
-      const bool b4 = hl & 16, b3 = hl & 8, b2 = hl & 4;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) r4[j] = (b4 ? acc[j + 4] : acc[j]) + __shfl_xor(b4 ? acc[j] : acc[j + 4], 16);
-#pragma unroll
-      for (int j = 0; j < 2; ++j) r2[j] = (b3 ? r4[j + 2] : r4[j]) + __shfl_xor(b3 ? r4[j] : r4[j + 2], 8);
-      r1 = (b2 ? r2[1] : r2[0]) + __shfl_xor(b2 ? r2[0] : r2[1], 4);
-      r1 += __shfl_xor(r1, 2);
-      r1 += __shfl_xor(r1, 1);
-      const int my_j = j0 + 4 * ((hl >> 4) & 1) + 2 * ((hl >> 3) & 1) + ((hl >> 2) & 1);
+      // the batch's squared distances in fp32, lane hl ending with that of candidate my_j
+      const float r1 = batch_dist2<32, float>(v, hl, nv, j0, n, [&](int jj) {
+        return reinterpret_cast<const float4*>(p.centers + (int64_t)cand_global(p, base, j0 + jj) * p.dim);
+      });
+      const int my_j = j0 + batch_slot<32>(hl);
       const bool real = my_j < n;
       const float lb = real ? r1 - r1 * eps : INFINITY;
       float ub = real ? fmaf(r1, eps, r1) + 1e-30f : INFINITY;
@@ -1253,7 +985,7 @@ __device__ __forceinline__ void rescreen_rows(const AssignParams& p, const int32
       U = fminf(U, ub);
 #pragma unroll
       for (int jj = 0; jj < kBatch; ++jj) {
-        const int src = (hh << 5) | (16 * ((jj >> 2) & 1) + 8 * ((jj >> 1) & 1) + 4 * (jj & 1));
+        const int src = (hh << 5) | batch_lane<32>(jj);
         const float lbj = __shfl(lb, src);
         const bool q = lbj <= U;
         if (q && cnt == kMaxList) {  // full: drop entries the current U already excludes (rare)

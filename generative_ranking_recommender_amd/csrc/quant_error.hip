@@ -6,7 +6,7 @@
 // centre it was given, the row norm, and deterministic fp64 totals.  The arithmetic is the fp32 operation
 // sequence of _compute_residuals_with_centers (hierarchical_rq_kmeans.py:1088-1128, res_normalize = 1) or of the
 // simplified generator's plain residuals (simplified_semantic_id_generator.py:78-96,164-168, res_normalize = 0),
-// i.e. that of rescore_rows (assign.hip) and of rqsid_residual with one dimension group.
+// i.e. that of exact_row.h (the float4 steps are its own) and of rqsid_residual with one dimension group.
 //
 // Shape: one wave per row, lanes over the row's dim/4 float4 pieces (16-byte loads only); a wave owns runs of
 // kQeRun consecutive positions of the processing order and works through a run two rows at a time, so that the
@@ -25,6 +25,7 @@
 #include <cstdint>
 
 #include "assign_common.h"
+#include "exact_row.h"  // sub4, div4, sq4
 
 namespace rqsid {
 namespace {
@@ -52,13 +53,6 @@ struct QeParams {
   int32_t normalize;
 };
 
-__device__ __forceinline__ float4 sub4(float4 a, float4 c) {
-  return make_float4(a.x - c.x, a.y - c.y, a.z - c.z, a.w - c.w);
-}
-__device__ __forceinline__ float4 div4(float4 a, float d) { return make_float4(a.x / d, a.y / d, a.z / d, a.w / d); }
-__device__ __forceinline__ double sq4(float4 a) {
-  return (double)a.x * a.x + (double)a.y * a.y + (double)a.z * a.z + (double)a.w * a.w;
-}
 __device__ __forceinline__ int clamp_id(int32_t id, int32_t k) { return (unsigned)id < (unsigned)k ? id : 0; }
 
 // the rows of one pair of positions and their last-level centre rows

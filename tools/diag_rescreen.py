@@ -2,7 +2,7 @@
 fp16 screen bound admits many candidates, with and without the fp32 re-screen, and histogram the work items
 the screen / re-screen left (n = -1: every candidate).  Inputs: 'iso' = random unit vectors; 'r2' = the
 bench's normalised level-2 residual rows (bench.fitted_codebooks' construction) against K of those rows
-(the first iteration of its K=2560 Lloyd fit)."""
+(the first iteration of its K=2560 Lloyd fit).  Arguments: the inputs to run (default: both)."""
 import json
 import os
 import sys
@@ -52,7 +52,10 @@ def main():
     dev = torch.device("cuda", 0)
     n, k = 1_000_000, 2560
     out = []
-    for kind in ("iso", "r2"):
+    kinds = sys.argv[1:] or ["iso", "r2"]
+    if any(k not in ("iso", "r2") for k in kinds):
+        sys.exit(f"usage: diag_rescreen.py [iso] [r2] (got {kinds})")
+    for kind in kinds:
         if kind == "iso":
             g = torch.Generator(device=dev).manual_seed(7)
             x = torch.nn.functional.normalize(torch.randn((n, 512), device=dev, generator=g), dim=1)
