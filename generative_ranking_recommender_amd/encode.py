@@ -590,6 +590,12 @@ class RQEncoder:
             raise RuntimeError("RQEncoder.quant_error: an id names no centre")
         return QuantError(ids, err, x_norm, rec[:, self.L - 1], sums, rec)
 
+    def cluster_report(self, x: torch.Tensor, ids: Optional[torch.Tensor] = None, **kw):
+        """The reference's quality check of these IDs (silhouette, Calinski-Harabasz, Davies-Bouldin per prefix depth,
+        in the original space): ``cluster_report.cluster_report(self, x, ids, **kw)``."""
+        from .cluster_report import cluster_report
+        return cluster_report(self, x, ids, **kw)
+
     def decode(self, ids: torch.Tensor, err: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Reconstruction f32 [N, D] of semantic IDs (plain torch gathers).  Plain residuals: the sum of the levels'
         centres.  Normalised residuals: ``c0 + d0 (c1 + d1 c2)`` with ``d_l = err[:, l] + 1e-8`` from ``quant_error``

@@ -971,6 +971,22 @@ class HierarchicalRQKMeans:
         x, comm = shard_rows(X, self.device, self.group)
         return margin_report(self._encoder(False), x, comm)
 
+    def cluster_quality(self, X: np.ndarray, sample: int = 50000, seed: int = 0, against: str = "all") -> Dict:
+        """The reference's own quality check (calculate_metrics.py: sklearn's silhouette, Calinski-Harabasz and
+        Davies-Bouldin scores of the ID tuples on the raw vectors) for the training-consistent IDs of ``X``, per
+        prefix depth (cluster_report.py has the keys).  Single process only: with a process group it raises."""
+        if not self.is_trained or not self.cluster_centers_list:
+            raise RuntimeError("Model not trained. Call train() first or load a trained model.")
+        if X.shape[1] != self.config.embedding_dim:
+            raise ValueError(f"Input dimension {X.shape[1]} does not match config embedding_dim "
+                             f"{self.config.embedding_dim}")
+        if self.group is not None:
+            raise NotImplementedError("cluster_quality: the multi-GPU form is not built (single process only)")
+        from .cluster_report import cluster_report
+        from .quant_report import shard_rows
+        x, _ = shard_rows(X, self.device, None)
+        return cluster_report(self._encoder(False), x, sample=sample, seed=seed, against=against)
+
     def gather_ids(self, ids_local: torch.Tensor) -> torch.Tensor:
         """All ranks' IDs in row order (one variable-size all_gather of int32 rows)."""
         if self.group is None:

@@ -8,7 +8,8 @@ distances of a row's nearest and second-nearest allowed centre at a level:
 * ``mean_margin`` / ``min_margin``: mean and minimum of ``d2 - d1`` over the ranked rows (a row with a small margin
   flips its ID when the embeddings move);
 * ``mean_silhouette``: mean of the simplified silhouette ``(d2 - d1) / d2`` (0 where d2 == 0), the cluster score
-  the reference's QA (calculate_metrics.py) takes from sklearn on a 50k sample, here over every row;
+  the reference's QA (calculate_metrics.py) takes from sklearn on a 50k sample, here over every row (centre-based:
+  the exact, pairwise score and the other two sklearn scores are ``cluster_report.py``'s);
 * ``share_below``: per threshold, the share of ranked rows whose silhouette is below it.
 
 Means of an empty set and the minimum of one are ``None``.  With a process group every rank passes its own shard;

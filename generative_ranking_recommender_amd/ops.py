@@ -613,6 +613,75 @@ def quant_error(x: torch.Tensor, centers: Sequence[torch.Tensor], ids: Sequence[
     return err.t(), x_norm, sums
 
 
+class SilhouetteWorkspace:
+    """Scratch of rqsid_silhouette: squared norms of rows and queries, one record per query and chunk and, in bytes
+    [0, 4), the sticky error word (1: a row_index / query_self entry outside the rows, 2: a query_seg entry outside
+    [-1, n_segments), 4: a seg_row_off entry outside [0, n_rows] or decreasing), zeroed here once."""
+
+    def __init__(self, n_rows: int, n_queries: int, device, chunk_rows: int = 0):
+        self.bytes = int(lib().rqsid_silhouette_workspace_bytes(n_rows, n_queries, chunk_rows))
+        if self.bytes < 0:
+            _lib.check(self.bytes, "rqsid_silhouette_workspace_bytes")
+        self.buf = torch.empty(max(self.bytes, 256), dtype=torch.uint8, device=device)
+        self.buf[:256].zero_()
+        self.n_rows, self.n_queries, self.chunk_rows = n_rows, n_queries, chunk_rows
+
+    def error_word(self) -> torch.Tensor:
+        return self.buf[:4].view(torch.int32)
+
+
+SILHOUETTE_WORD = ("bit 1: a row_index or query_self entry outside [0, n_rows) was skipped; bit 2: a query_seg entry "
+                   "outside [-1, n_segments) was taken as -1; bit 4: a seg_row_off entry outside [0, n_rows] or "
+                   "decreasing was clamped (include/rqsid.h rqsid_silhouette)")
+
+
+def silhouette_tile_rows() -> int:
+    return int(lib().rqsid_silhouette_tile_rows())
+
+
+def silhouette(x: torch.Tensor, order: Optional[torch.Tensor], seg_row_off: torch.Tensor, q: torch.Tensor,
+               query_self: Optional[torch.Tensor], query_seg: Optional[torch.Tensor], chunk_rows: int = 0,
+               workspace: Optional[SilhouetteWorkspace] = None, check: Optional[bool] = None):
+    """Exact silhouette sums of the rows ``q`` against the clusters of ``x`` (include/rqsid.h rqsid_silhouette).
+
+    ``x``: float32 / float16 / bfloat16 [N, D]; ``order``: i32 [N], the rows grouped by cluster (``Buckets.row_index``;
+    None = identity); ``seg_row_off``: i32 [S + 1]; ``q``: [M, D] of x's dtype; ``query_self``: i32 [M], the row of x
+    that is the query, or -1 (None = all -1); ``query_seg``: i32 [M], the query's own cluster, or -1 (None = all -1).
+    Returns ``(a, b, b_seg, s)``: f32 [M], f32 [M], i32 [M], f32 [M].  ``check`` (default: on unless the stream is being
+    captured): read the workspace's error word after the call (one host sync) and raise if a table entry was clamped."""
+    if check is None:
+        check = not torch.cuda.is_current_stream_capturing()
+    x_format = ROW_FORMATS.get(x.dtype)
+    if x_format is None:
+        raise ValueError(f"rqsid_silhouette reads float32, float16 or bfloat16 rows, not {x.dtype}")
+    if x.dim() != 2 or q.dim() != 2 or q.shape[1] != x.shape[1] or q.dtype != x.dtype:
+        raise ValueError("rqsid_silhouette: x [N, D] and q [M, D] must share dtype and D")
+    _require_device(x, order, seg_row_off, q, query_self, query_seg)
+    n, d = x.shape
+    m = q.shape[0]
+    if order is not None and (order.dtype != torch.int32 or order.numel() != n):
+        raise ValueError("rqsid_silhouette: order must be int32 [N]")
+    if seg_row_off.dtype != torch.int32 or seg_row_off.dim() != 1 or seg_row_off.numel() < 2:
+        raise ValueError("rqsid_silhouette: seg_row_off must be int32 [S + 1]")
+    for name, t in (("query_self", query_self), ("query_seg", query_seg)):
+        if t is not None and (t.dtype != torch.int32 or t.numel() != m):
+            raise ValueError(f"rqsid_silhouette: {name} must be int32 [M]")
+    dev = x.device
+    a = torch.empty(m, dtype=torch.float32, device=dev)
+    b = torch.empty(m, dtype=torch.float32, device=dev)
+    b_seg = torch.empty(m, dtype=torch.int32, device=dev)
+    s = torch.empty(m, dtype=torch.float32, device=dev)
+    if workspace is None or workspace.bytes < int(lib().rqsid_silhouette_workspace_bytes(n, m, chunk_rows)):
+        workspace = SilhouetteWorkspace(n, m, dev, chunk_rows)
+    _lib.check(lib().rqsid_silhouette(_ptr(x), x_format, n, d, _ptr(order), seg_row_off.numel() - 1, _ptr(seg_row_off),
+                                      _ptr(q), m, _ptr(query_self), _ptr(query_seg), chunk_rows, _ptr(a), _ptr(b),
+                                      _ptr(b_seg), _ptr(s), _ptr(workspace.buf), workspace.bytes, _stream()),
+               "rqsid_silhouette")
+    if check:
+        check_error_words([workspace.error_word()], "rqsid_silhouette", SILHOUETTE_WORD)
+    return a, b, b_seg, s
+
+
 def scale_groups(x: torch.Tensor, group_dims: Sequence[int], weights: Sequence[float]) -> torch.Tensor:
     _require_device(x)
     n, d = x.shape

@@ -31,8 +31,16 @@ class SemanticIDTrainer:
     """train_semantic_ids.py:35-365."""
 
     def __init__(self, config, use_test_config: bool = False, device=None, group=None,
-                 report_quantization: bool = False, report_margins: bool = False, report_beam: int = 0):
+                 report_quantization: bool = False, report_margins: bool = False, report_beam: int = 0,
+                 report_clusters: int = 0):
         self.config = config
+        # opt-in (a sample size, the reference's is 50000): also write cluster_quality_report.json
+        # (HierarchicalRQKMeans.cluster_quality of the training rows: the three scores of the reference's
+        # calculate_metrics.py per prefix depth).  Single process only: refused here, before any training
+        self.report_clusters = int(report_clusters or 0)
+        if group is not None and self.report_clusters:
+            raise NotImplementedError("SemanticIDTrainer: report_clusters is single-process only (the multi-GPU "
+                                      "cluster report is not built)")
         # opt-in (a beam width 1..8): also write beam_report.json (HierarchicalRQKMeans.beam_report of the training
         # rows: what a beam-search encode of that width would change and gain); the IDs written stay greedy
         self.report_beam = int(report_beam or 0)
@@ -103,6 +111,10 @@ class SemanticIDTrainer:
             if self.rank == 0:
                 rq_io.write_json(str(self.output_dir / "beam_report.json"), beam)
             result["beam_report"] = beam
+        if self.report_clusters:
+            clusters = model.cluster_quality(vectors, sample=self.report_clusters)
+            rq_io.write_json(str(self.output_dir / "cluster_quality_report.json"), clusters)
+            result["cluster_quality_report"] = clusters
         return result
 
     def _generate_semantic_ids(self, song_ids: list, train_result: Dict) -> Dict:

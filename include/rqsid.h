@@ -303,6 +303,48 @@ int rqsid_quant_error(const void* x, int32_t x_format, int64_t n_rows, int32_t d
                       float* err, float* x_norm, double* sums,
                       void* workspace, int64_t workspace_bytes, void* stream);
 
+/* Exact silhouette sums of scored rows against every cluster: the pairwise half of the reference's
+ * quality check, sklearn's silhouette_score on the raw vectors (src/semantic_id_generator/calculate_metrics.py),
+ * without materialising any distance matrix.
+ * Cluster c is the set of rows row_index[seg_row_off[c] .. seg_row_off[c+1]) (row_index NULL = identity; the output
+ * of rqsid_bucket over the labels serves as it is), n_c its size, d(i, j) the Euclidean distance.  Query i (row i of
+ * q, [n_queries][dim] in x_format like x) has own cluster o = query_seg[i] (-1: none; query_seg NULL = all -1) and
+ * self row r = query_self[i] (the row of x that IS this query, or -1; NULL = all -1):
+ *   S(i, c) = sum over j in c, j != r, of d(i, j);
+ *   a = S(i, o) / (n_o - 1) with a self row, S(i, o) / n_o without (0 when that divisor is 0, and when o = -1);
+ *   b = min over non-empty c != o of S(i, c) / n_c, lowest c on an exact tie; out_b_seg = that c;
+ *   s = (b - a) / max(a, b); 0 when max(a, b) = 0, and (sklearn's rule) 0 for a query with a self row whose own
+ *   cluster has one row.  With o = -1 every cluster competes for b (the caller ignores s).  No other non-empty
+ *   cluster: b = +inf, out_b_seg = -1, s = NaN.
+ * The self row is excluded by INDEX, never by value (the expanded form below does not return 0 for d(i, i)).  A
+ * non-finite value reaching a sum makes that query's a / b / s NaN (out_b_seg -1); it is not an error.
+ * Arithmetic: d = fl32(sqrt(max(0, fl32(|q|^2 + |x_j|^2) - 2 D))) with D the dot product on v_mfma_f32_32x32x2_f32
+ * (bitwise an fmaf chain over the dims in order; 3.1g's bound on |D - q.x| applies) and the squared norms
+ * accumulated in fp64 and rounded once, as c_meta's.  Distances are added in fp32 inside one (tile, cluster) piece
+ * of at most rqsid_silhouette_tile_rows() consecutive positions of the bucketed order, in position order; pieces,
+ * chunks and the divisions are fp64, in a fixed order; a and b are rounded to fp32 once, at the store, and s is
+ * formed from the fp64 values.  No float atomics: two calls with the same arguments return identical bytes, and
+ * chunk_rows moves only fp64 roundings.  RQSID_X_F16 / RQSID_X_BF16 rows and queries are widened as they are staged
+ * (no fp32 copy of them anywhere); the outputs are bit-identical to the call on the widened fp32 rows.
+ * Limits: dim % 32 == 0, dim <= 1024; n_rows < 2^31; x and q 16-byte aligned; chunk_rows (base positions per block)
+ * 0 = automatic (the fewest chunks that give 2048 blocks) or a positive multiple of the tile rows; n_queries == 0
+ * or n_rows == 0 succeeds without touching anything.  RQSID_E_ARG / RQSID_E_WORKSPACE before any HIP call.
+ * Stream-ordered, no host synchronisation, graph-capturable.
+ * Workspace (rqsid_silhouette_workspace_bytes: the header, the squared norms of rows and queries, one 48-byte
+ * record per query and chunk): bytes [0, 4) are a sticky error word the caller zeroes when it allocates the
+ * workspace (a call never clears it): 1 = a row_index or query_self entry outside [0, n_rows) (query_self: other
+ * than -1; the entry is skipped / taken as -1), 2 = a query_seg entry outside [-1, n_segments) (taken as -1), 4 = a
+ * seg_row_off entry outside [0, n_rows] or decreasing (clamped into [0, n_rows]; positions no cluster owns are left
+ * out).  No address is formed from an unchecked index: rows are addressed by position inside [0, n_rows) and by
+ * row_index entries inside it, and the offsets only place boundaries. */
+int32_t rqsid_silhouette_tile_rows(void);
+int64_t rqsid_silhouette_workspace_bytes(int64_t n_rows, int32_t n_queries, int32_t chunk_rows);
+int rqsid_silhouette(const void* x, int32_t x_format, int64_t n_rows, int32_t dim,
+                     const int32_t* row_index, int32_t n_segments, const int32_t* seg_row_off,
+                     const void* q, int32_t n_queries, const int32_t* query_self, const int32_t* query_seg,
+                     int32_t chunk_rows, float* out_a, float* out_b, int32_t* out_b_seg, float* out_s,
+                     void* workspace, int64_t workspace_bytes, void* stream);
+
 /* y = x * w_g per dimension group (hierarchical_rq_kmeans.py:583-604). */
 int rqsid_scale_groups(const float* x, int64_t n, int32_t dim, const int32_t* group_dims,
                        int32_t n_groups, const float* weights, float* out, void* stream);
