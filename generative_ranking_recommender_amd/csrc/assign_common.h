@@ -336,6 +336,78 @@ __device__ __forceinline__ bool pass_decide(const uint32_t (&pbits)[NW], int h, 
   return definitive;
 }
 
+// The same decision from pass words in natural bit order, all NW words of a row in one lane (bit b of word t:
+// candidate 32 t + b; the transposed epilogue of assign_pc.hip).  definitive: exactly one candidate passed
+// (k_out); else the work item lists the (<= kMaxList, ascending) passing candidates or -1 (none or more
+// passed: re-score every candidate).  Lanes that own no row pass zero words.
+template <int NW>
+__device__ __forceinline__ int pass_take_lowest(uint32_t (&wv)[NW]) {
+  int ws = -1;
+  uint32_t b = 0;
+#pragma unroll
+  for (int w = NW - 1; w >= 0; --w) {
+    const bool nz = wv[w] != 0;
+    ws = nz ? w : ws;
+    b = nz ? wv[w] : b;
+  }
+  const int k = ws >= 0 ? 32 * ws + (__ffs((int)b) - 1) : -1;
+#pragma unroll
+  for (int w = 0; w < NW; ++w) wv[w] = w == ws ? (b & (b - 1u)) : wv[w];
+  return k;
+}
+template <int NW>
+__device__ __forceinline__ bool pass_decide_words(const uint32_t (&pw)[NW], int& k_out, WorkItem& w) {
+  int pc = 0;
+#pragma unroll
+  for (int i = 0; i < NW; ++i) pc += __popc(pw[i]);
+  const bool overflow = pc > kMaxList || pc == 0;
+  const bool definitive = pc == 1;
+  uint32_t wv[NW];
+#pragma unroll
+  for (int i = 0; i < NW; ++i) wv[i] = pw[i];
+  k_out = pass_take_lowest(wv);
+  w.n = overflow ? -1 : pc;
+  const bool listed = !definitive && !overflow;
+  if (__builtin_amdgcn_ballot_w64(listed)) {  // wave-uniform: some row needs a list
+    w.cand[0] = (uint16_t)(k_out >= 0 ? k_out : 0xFFFF);
+#pragma unroll
+    for (int j = 1; j < kMaxList; ++j) w.cand[j] = 0xFFFF;
+#pragma unroll
+    for (int j = 1; j < kMaxList; ++j) {  // as many extractions as the longest list of the wave has entries
+      if (!__builtin_amdgcn_ballot_w64(listed && pc > j)) break;
+      const int k = pass_take_lowest(wv);
+      w.cand[j] = (uint16_t)(k >= 0 ? k : 0xFFFF);
+    }
+  }
+  return definitive;
+}
+
+// Minimum over the 32 lanes of each wave half of four values at once, left in every lane of the half: four
+// DPP steps inside the rows of 16 lanes (lane ^ 1, lane ^ 2, then the mirrors, exact once the quads / eights
+// are uniform) and one v_permlane16_swap between the two rows.  The four chains are interleaved so that every
+// DPP / swap reads a register written at least three instructions earlier (two wait states are required);
+// the leading s_nop covers the caller's last write.  All 64 lanes must be active.
+__device__ __forceinline__ void half_min4(float& a, float& b, float& c, float& d) {
+  float ta, tb, tc, td;
+#define RQ_MIN4(ctl)                                                  \
+  "v_min_f32_dpp %0, %0, %0 " ctl " row_mask:0xf bank_mask:0xf\n\t"   \
+  "v_min_f32_dpp %1, %1, %1 " ctl " row_mask:0xf bank_mask:0xf\n\t"   \
+  "v_min_f32_dpp %2, %2, %2 " ctl " row_mask:0xf bank_mask:0xf\n\t"   \
+  "v_min_f32_dpp %3, %3, %3 " ctl " row_mask:0xf bank_mask:0xf\n\t"
+  asm volatile(
+      "s_nop 1\n\t"
+      RQ_MIN4("quad_perm:[1,0,3,2]")
+      RQ_MIN4("quad_perm:[2,3,0,1]")
+      RQ_MIN4("row_half_mirror")
+      RQ_MIN4("row_mirror")
+      "v_mov_b32 %4, %0\n\tv_mov_b32 %5, %1\n\tv_mov_b32 %6, %2\n\tv_mov_b32 %7, %3\n\t"
+      "v_permlane16_swap_b32 %4, %0\n\tv_permlane16_swap_b32 %5, %1\n\t"
+      "v_permlane16_swap_b32 %6, %2\n\tv_permlane16_swap_b32 %7, %3\n\t"
+      "v_min_f32 %0, %0, %4\n\tv_min_f32 %1, %1, %5\n\tv_min_f32 %2, %2, %6\n\tv_min_f32 %3, %3, %7"
+      : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "=&v"(ta), "=&v"(tb), "=&v"(tc), "=&v"(td));
+#undef RQ_MIN4
+}
+
 __device__ __forceinline__ float ratio_up(float num, float den) {
   return den > 0.f ? num / den * 1.000001f : (num > 0.f ? INFINITY : 0.f);
 }

@@ -12,9 +12,14 @@
 //  * Waves 0-3 are CONSUMERS (one per SIMD): each owns 32 rows of the tile and runs only LDS fragment
 //    reads, MFMAs (32 rows x all candidates, 128 accumulator registers) and the tile's bound epilogue and
 //    output stores.  They issue no global load, so no wave that computes ever stalls on DMA issue.
+//    The rows are the MFMA's A operand and the centres its B operand (the two fragments have the same lane
+//    layout), so acc[t][v] of lane (h, r) is candidate 32t + r and row 8(v>>2) + 4h + (v&3) of the wave's 32:
+//    in the epilogue the per-candidate |c|^2 and |c| are 2 NT registers of the lane, the per-row {m2, A2} are
+//    broadcast reads shared by all NT tiles, the row minimum U goes over the lanes (half_min4) and the lane
+//    mask of one compare is a row's 32-candidate pass word.
 //  * Waves 4-7 are ROW PRODUCERS (one per SIMD, beside a consumer): they issue the row chunks'
 //    global_load_lds (from HBM, four chunks ahead), run the fused residual chain on the landed fp32 rows and
-//    write the MFMA B operand (fp16 rows, and their rounding residuals for the 3-term screen) into a
+//    write the MFMA row operand B (fp16 rows, and their rounding residuals for the 3-term screen) into a
 //    double-buffered LDS image, and reduce the rows' bound coefficients {m2, A2} once per tile.  So the
 //    residual chain's VALU of one wave runs beside the MFMAs of the other wave on the same SIMD.
 //  * Waves 8-11 are LOADERS (one per SIMD): the candidates' fp16 centre chunks two ahead and the next
@@ -34,7 +39,9 @@
 
 #ifdef RQSID_STAMPS
 // diagnostic build only (tools/pc_stamps.py): per role (0 consumer, 1 row producer, 2 loader) lane 0 of every
-// wave adds {total, barrier, vmcnt wait, epilogue / finish, waves, compute / build, DMA issue, -} cycles
+// wave adds {total, barrier, vmcnt wait, epilogue / finish, waves, compute / build, DMA issue, -} cycles; the
+// consumers also the parts of their epilogue: [2], [6], [7], [23], and inside [6] the bound [15], the row minimum
+// [19] and the pass words [21] (these three stamps wait for the coefficient prefetch: read them as an upper bound)
 __device__ unsigned long long g_pc_stamps[24];
 #define PST(...) __VA_ARGS__
 #define PNOW() __builtin_amdgcn_s_memtime()
@@ -76,7 +83,8 @@ struct PcLayout {
   static constexpr int kHDen = kHY + NT * 128;                      //   128 f32 den_in (RL 2)
   static constexpr int kHRes = kHDen + kQRows * 4;                  //   RL x 512 f32 residual centre rows
   static constexpr int kHBytes = kHRes + RL * kQDim * 4;
-  static constexpr int kCoef = kH + 2 * kHBytes;                    // 128 x {m2, A2, den, -}
+  static constexpr int kCoef = kH + 2 * kHBytes;                    // the rows' m2[128], A2[128], den[128]
+  static constexpr int kCoefA2 = kQRows * 4, kCoefDen = 2 * kQRows * 4;
   static constexpr int kBytes = kCoef + kQRows * 16;
   static constexpr int kCI = NT / 2;                                // centre DMA ops per loader per table
   static constexpr int H = 3;                                       // ops of each header level
@@ -112,6 +120,41 @@ __device__ __forceinline__ void dma4(const void* gsrc, uint32_t lds_base) {
       : "v"(gsrc), "s"(lds_base)
       : "memory");
 }
+// Lane masks m[t] of NT compares into lanes LANE (low words) and LANE + 4 (high words) of v[t].  The compares
+// are the compiler's and these lane writes are not instructions it knows, so the block keeps the distances the
+// hardware wants itself: two wait states between a VALU write of an SGPR and its VALU read (the leading s_nop:
+// the last compare may sit right in front), one between two lane writes of a register (NT others lie between)
+template <int LANE>
+__device__ __forceinline__ void write_lanes(uint32_t (&v)[8], const uint64_t (&m)[8]) {
+#define RQ_L(t) (uint32_t)m[t]
+#define RQ_H(t) (uint32_t)(m[t] >> 32)
+  asm volatile(
+      "s_nop 1\n\t"
+      "v_writelane_b32 %0, %8, %24\n\tv_writelane_b32 %1, %9, %24\n\tv_writelane_b32 %2, %10, %24\n\t"
+      "v_writelane_b32 %3, %11, %24\n\tv_writelane_b32 %4, %12, %24\n\tv_writelane_b32 %5, %13, %24\n\t"
+      "v_writelane_b32 %6, %14, %24\n\tv_writelane_b32 %7, %15, %24\n\t"
+      "v_writelane_b32 %0, %16, %25\n\tv_writelane_b32 %1, %17, %25\n\tv_writelane_b32 %2, %18, %25\n\t"
+      "v_writelane_b32 %3, %19, %25\n\tv_writelane_b32 %4, %20, %25\n\tv_writelane_b32 %5, %21, %25\n\t"
+      "v_writelane_b32 %6, %22, %25\n\tv_writelane_b32 %7, %23, %25"
+      : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]), "+v"(v[7])
+      : "s"(RQ_L(0)), "s"(RQ_L(1)), "s"(RQ_L(2)), "s"(RQ_L(3)), "s"(RQ_L(4)), "s"(RQ_L(5)), "s"(RQ_L(6)), "s"(RQ_L(7)),
+        "s"(RQ_H(0)), "s"(RQ_H(1)), "s"(RQ_H(2)), "s"(RQ_H(3)), "s"(RQ_H(4)), "s"(RQ_H(5)), "s"(RQ_H(6)), "s"(RQ_H(7)),
+        "n"(LANE), "n"(LANE + 4));
+}
+template <int LANE>
+__device__ __forceinline__ void write_lanes(uint32_t (&v)[4], const uint64_t (&m)[4]) {
+  asm volatile(
+      "s_nop 1\n\t"
+      "v_writelane_b32 %0, %4, %12\n\tv_writelane_b32 %1, %5, %12\n\tv_writelane_b32 %2, %6, %12\n\t"
+      "v_writelane_b32 %3, %7, %12\n\t"
+      "v_writelane_b32 %0, %8, %13\n\tv_writelane_b32 %1, %9, %13\n\tv_writelane_b32 %2, %10, %13\n\t"
+      "v_writelane_b32 %3, %11, %13"
+      : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3])
+      : "s"(RQ_L(0)), "s"(RQ_L(1)), "s"(RQ_L(2)), "s"(RQ_L(3)), "s"(RQ_H(0)), "s"(RQ_H(1)), "s"(RQ_H(2)), "s"(RQ_H(3)),
+        "n"(LANE), "n"(LANE + 4));
+#undef RQ_L
+#undef RQ_H
+}
 template <int N>
 __device__ __forceinline__ void vm_lgkm_barrier() {
   asm volatile("s_waitcnt vmcnt(%0)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" ::"i"(N) : "memory");
@@ -140,13 +183,21 @@ __global__ __launch_bounds__(768, 3) void assign_pc_kernel(AssignParams p, const
   if (wave < 4) {
     // ================================ consumer (wave c = rows 32c .. 32c+31) ================================
     const int c = wave;
-    const int csw = (r >> 2) & 3;  // centre image swizzle of this lane's candidate rows
+    // the lane, taken anew wherever it is needed (volatile: not hoisted): the accumulators leave no register for
+    // a lane-derived address to live through the tile's epilogue
+    auto lane_now = [&]() __attribute__((always_inline)) {
+      int ln;
+      asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(ln));
+      return ln;
+    };
     f32x16 acc[NT];
     f32x16 accl[T3 ? NT : 1];
     // MFMAs of chunk g from B(g) (stage g & 1) and C(g) (stage g % 3); FIRST: the tile's first chunk
     // (zero accumulators in, a compile-time choice: the call sites pass a literal)
     auto compute = [&](int g, bool first) __attribute__((always_inline)) {
       const f32x16 zero16 = {};
+      const int lane = lane_now(), h = lane >> 5, r = lane & 31;
+      const int csw = (r >> 2) & 3;  // centre image swizzle of this lane's candidate rows
       const unsigned char* bimg = smem + L::kB + (g & 1) * L::kBS + c * L::kBW + lane * 16;
       const unsigned char* cimg0 = smem + L::kC + (g % L::Sc) * L::kCS + r * 64;
       f16x8 bf[2], bl[2];
@@ -161,18 +212,18 @@ __global__ __launch_bounds__(768, 3) void assign_pc_kernel(AssignParams p, const
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
           const f16x8 af = *reinterpret_cast<const f16x8*>(cimg + t * 32 * 64);
-          acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af, bf[ks], (first && ks == 0) ? zero16 : acc[t], 0, 0, 0);
+          acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bf[ks], af, (first && ks == 0) ? zero16 : acc[t], 0, 0, 0);
           if (T3) {
             const f16x8 al = *reinterpret_cast<const f16x8*>(cimg + L::kCT + t * 32 * 64);
-            accl[T3 ? t : 0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af, bl[ks], (first && ks == 0) ? zero16 : accl[T3 ? t : 0],
+            accl[T3 ? t : 0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bl[ks], af, (first && ks == 0) ? zero16 : accl[T3 ? t : 0],
                                                                       0, 0, 0);
-            accl[T3 ? t : 0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bf[ks], accl[T3 ? t : 0], 0, 0, 0);
+            accl[T3 ? t : 0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bf[ks], al, accl[T3 ? t : 0], 0, 0, 0);
           }
         }
       }
     };
     // epilogue of tile T (its {m2, A2} were written by the producers in the phase before)
-    PST(uint64_t s_eM = 0, s_eU = 0, s_eB = 0, s_eD = 0;)
+    PST(uint64_t s_eM = 0, s_eU = 0, s_eB = 0, s_eD = 0, s_g1 = 0, s_g2 = 0, s_g3 = 0;)
     auto epilogue = [&](const PcDesc& D, int par) __attribute__((always_inline)) {
 #ifdef RQSID_STAMPS
       uint64_t e0 = PNOW();
@@ -185,10 +236,6 @@ __global__ __launch_bounds__(768, 3) void assign_pc_kernel(AssignParams p, const
       e0 = PNOW();
 #endif
       const unsigned char* hb = smem + L::kH + par * L::kHBytes;
-      const int lr = 32 * c + r;
-      const bool row_valid = lr < D.nrows;
-      const int my_row = p.row_index ? reinterpret_cast<const int*>(hb + L::kHRow)[min(lr, D.nrows - 1)]
-                                     : D.t0 + min(lr, D.nrows - 1);
       auto cand_of = [&](int k) -> int {
         if (D.flags & 1) return 0;
         if (!p.cand_idx) return D.cbase + min(k, D.cnt - 1);
@@ -197,88 +244,117 @@ __global__ __launch_bounds__(768, 3) void assign_pc_kernel(AssignParams p, const
       int out_l = kQSentinel, out_g = kQSentinel;
       bool need = false;
       WorkItem w{};
-      w.row = my_row;
-      w.seg = D.s;
       if (D.flags & 1) {
         need = true;
         w.n = (D.flags & 2) ? -2 : -3;
       } else {
-        const float4 rc = *reinterpret_cast<const float4*>(smem + L::kCoef + lr * 16);
         // per candidate P = m2 d + |c|^2, E = A2 |c| (+ 1e-30); ub = P + E, lb = P - E, U = min ub, and a
-        // candidate passes iff lb <= U' (the pp / per-tile epilogue).  Here ub and lb are one FMA each on P
-        // and the two 1e-30 terms move into U' (lb - 1e-30 <= U + 1e-30 <=> lb <= U + 2e-30): the same test
-        const f2 m2v = {rc.x, rc.x}, a2v = {rc.y, rc.y}, na2v = {-rc.y, -rc.y};
-        const float* m_csq = reinterpret_cast<const float*>(hb + L::kHCsq);
-        const float* m_y = reinterpret_cast<const float*>(hb + L::kHY);
-        float U = INFINITY;
+        // candidate passes iff lb < U' (the pp / per-tile epilogue).  Here ub and lb are one FMA each on P
+        // and the two 1e-30 terms move into U' (lb - 1e-30 < U + 1e-30 <=> lb < U + 2e-30): the same test.
+        // The lane owns candidate 32t + r of every tile t, so |c|^2 and |c| are 2 NT registers read once,
+        // and rows 8gq + 4h + i (i < 4) of group gq, whose {m2, A2} are two 16-B broadcast reads per group:
+        // the loop over the accumulators reads no LDS
+        const int lane = lane_now(), h = lane >> 5, r = lane & 31;
+        const float* m_csq = reinterpret_cast<const float*>(hb + L::kHCsq) + r;
+        const float* m_y = reinterpret_cast<const float*>(hb + L::kHY) + r;
+        f2 cy[NT];  // {|c|^2, |c|} of candidate 32t + r: one register pair, either half broadcast by op_sel
 #pragma unroll
-        for (int t = 0; t < NT; ++t) {
+        for (int t = 0; t < NT; ++t) cy[t] = f2{m_csq[t * 32], m_y[t * 32]};
 #pragma unroll
-          for (int gq = 0; gq < 4; ++gq) {
-            const float4 csq = *reinterpret_cast<const float4*>(m_csq + t * 32 + 8 * gq + 4 * h);
-            const float4 yy = *reinterpret_cast<const float4*>(m_y + t * 32 + 8 * gq + 4 * h);
+        for (int t = 0; t < NT; t += 4)  // (kept as these pairs: a splat of either value would take a pair of its own)
+          asm("" : "+v"(cy[t]), "+v"(cy[t + 1]), "+v"(cy[t + 2]), "+v"(cy[t + 3]));
+        const unsigned char* coef = smem + L::kCoef + (32 * c + 4 * h) * 4;
+        float4 m2q = *reinterpret_cast<const float4*>(coef);
+        float4 a2q = *reinterpret_cast<const float4*>(coef + L::kCoefA2);
+        uint32_t pw[NT];  // lane j < 32: the pass words of row j (bit b of word t: candidate 32t + b)
 #pragma unroll
-            for (int e = 0; e < 2; ++e) {
-              const int v = 4 * gq + 2 * e;
-              f2 d = {acc[t][v], acc[t][v + 1]};
-              if (T3) d = f2{accl[T3 ? t : 0][v], accl[T3 ? t : 0][v + 1]} * 0x1p-12f + d;
-              const f2 P2 = m2v * d + (e ? f2{csq.z, csq.w} : f2{csq.x, csq.y});
-              const f2 y2 = e ? f2{yy.z, yy.w} : f2{yy.x, yy.y};
-              const f2 ub = a2v * y2 + P2, lb = na2v * y2 + P2;
-              U = fminf(U, fminf(ub.x, ub.y));
-              acc[t][v] = lb.x;
-              acc[t][v + 1] = lb.y;
+        for (int t = 0; t < NT; ++t) pw[t] = 0u;
+#pragma unroll
+        for (int gq = 0; gq < 4; ++gq) {
+          PST(uint64_t g0 = PNOW();)
+          float U[4] = {INFINITY, INFINITY, INFINITY, INFINITY};
+#pragma unroll
+          for (int e = 0; e < 2; ++e) {
+            const f2 m2v = e ? f2{m2q.z, m2q.w} : f2{m2q.x, m2q.y};
+            const f2 a2v = e ? f2{a2q.z, a2q.w} : f2{a2q.x, a2q.y};
+            const f2 na2v = -a2v;
+            const int v = 4 * gq + 2 * e;
+#pragma unroll
+            for (int t = 0; t < NT; t += 2) {
+              f2 ub[2];
+#pragma unroll
+              for (int u = 0; u < 2; ++u) {
+                f2 d = {acc[t + u][v], acc[t + u][v + 1]};
+                if (T3) d = f2{accl[T3 ? t + u : 0][v], accl[T3 ? t + u : 0][v + 1]} * 0x1p-12f + d;
+                const f2 P2 = m2v * d + __builtin_shufflevector(cy[t + u], cy[t + u], 0, 0);
+                const f2 y2 = __builtin_shufflevector(cy[t + u], cy[t + u], 1, 1);
+                const f2 lb = na2v * y2 + P2;
+                ub[u] = a2v * y2 + P2;
+                acc[t + u][v] = lb.x;
+                acc[t + u][v + 1] = lb.y;
+              }
+              U[2 * e] = fminf(U[2 * e], fminf(ub[0].x, ub[1].x));
+              U[2 * e + 1] = fminf(U[2 * e + 1], fminf(ub[0].y, ub[1].y));
+              __builtin_amdgcn_sched_barrier(0);  // lb replaces d in place: no second copy of the accumulators
             }
           }
-        }
-        U = fminf(U, xor32(U));
-        const float Up = fmaf(fabsf(U), 0x1p-22f, U) + (1.2e-38f + 2e-30f);
-        PST(asm volatile("" ::"v"(Up)); s_eU += PNOW() - e0; e0 = PNOW();)
-        const f2 upv = {Up, Up};
-        uint32_t pbt[NT];
-#pragma unroll
-        for (int t = 0; t < NT; ++t) pbt[t] = 0u;
-#pragma unroll
-        for (int v = 0; v < 16; v += 2)
-#pragma unroll
-          for (int t = 0; t < NT; ++t) {
-            const f2 d = f2{acc[t][v], acc[t][v + 1]} - upv;
-            pbt[t] = __builtin_amdgcn_alignbit(pbt[t], __float_as_uint(d.x), 31);
-            pbt[t] = __builtin_amdgcn_alignbit(pbt[t], __float_as_uint(d.y), 31);
+          if (gq < 3) {  // the next group's coefficients land behind this group's minimum and compares
+            m2q = *reinterpret_cast<const float4*>(coef + (gq + 1) * 32);
+            a2q = *reinterpret_cast<const float4*>(coef + L::kCoefA2 + (gq + 1) * 32);
           }
-        uint32_t pbits[NT / 2];
+          __builtin_amdgcn_sched_barrier(0);
+          PST(asm volatile("" ::"v"(U[0]), "v"(U[3])); s_g1 += PNOW() - g0; g0 = PNOW();)
+          half_min4(U[0], U[1], U[2], U[3]);  // U of rows 8gq + 4h + i in every lane of half h
+          PST(asm volatile("" ::"v"(U[0]), "v"(U[3])); s_g2 += PNOW() - g0; g0 = PNOW();)
+          // one compare per tile and row pair: its lane mask is the 32-candidate pass word of row 8gq + i (low
+          // half) and of row 8gq + 4 + i (high half), in ascending candidate order
+          auto pass_words = [&](auto I) __attribute__((always_inline)) {
+            constexpr int i = decltype(I)::value;
+            const float Up = fmaf(fabsf(U[i]), 0x1p-22f, U[i]) + (1.2e-38f + 2e-30f);
+            uint64_t m[NT];
 #pragma unroll
-        for (int wd = 0; wd < NT / 2; ++wd) pbits[wd] = (pbt[2 * wd] << 16) | pbt[2 * wd + 1];
+            for (int t = 0; t < NT; ++t) m[t] = __builtin_amdgcn_ballot_w64(acc[t][4 * gq + i] < Up);
+            switch (gq) {  // (the lane is a literal of the instruction)
+              case 0: write_lanes<i>(pw, m); break;
+              case 1: write_lanes<8 + i>(pw, m); break;
+              case 2: write_lanes<16 + i>(pw, m); break;
+              default: write_lanes<24 + i>(pw, m); break;
+            }
+          };
+          pass_words(std::integral_constant<int, 0>());
+          pass_words(std::integral_constant<int, 1>());
+          pass_words(std::integral_constant<int, 2>());
+          pass_words(std::integral_constant<int, 3>());
+          PST(asm volatile("" ::"v"(pw[0]), "v"(pw[NT - 1])); s_g3 += PNOW() - g0;)
+          __builtin_amdgcn_sched_barrier(0);  // one group at a time: its 4 NT lower bounds are dead from here
+        }
+        PST(asm volatile("" ::"v"(pw[0]), "v"(pw[NT - 1])); s_eU += PNOW() - e0; e0 = PNOW();)
         if (D.cnt < NT * 32) {  // candidates beyond cnt (duplicates of the last one) never pass
 #pragma unroll
-          for (int wd = 0; wd < NT / 2; ++wd) {
-            uint32_t m = 0;
-#pragma unroll
-            for (int qq = 0; qq < 2; ++qq) {
-              const int rem = D.cnt - 32 * (2 * wd + qq) - 4 * h;  // valid iff (v&3) + 8(v>>2) < rem
-              int nv = 0;
-#pragma unroll
-              for (int gq = 0; gq < 4; ++gq) nv += min(4, max(0, rem - 8 * gq));
-              const uint32_t pre = (uint32_t)((0xFFFFull << (16 - nv)) & 0xFFFFull);
-              m |= qq == 0 ? pre << 16 : pre;
-            }
-            pbits[wd] &= m;
+          for (int t = 0; t < NT; ++t) {
+            const int nv = min(32, max(0, D.cnt - 32 * t));
+            pw[t] &= (uint32_t)((1ull << nv) - 1ull);
           }
         }
-        PST(asm volatile("" ::"v"(pbits[0]), "v"(pbits[NT / 2 - 1])); s_eB += PNOW() - e0; e0 = PNOW();)
+        PST(asm volatile("" ::"v"(pw[0]), "v"(pw[NT - 1])); s_eB += PNOW() - e0; e0 = PNOW();)
         int k = -1;
-        if (pass_decide(pbits, h, k, w)) {
+        if (pass_decide_words(pw, k, w)) {
           out_l = p.cand_lid ? cand_local(p, D.cbase, k) : k;  // (a deduplicated list reports the original local id)
           out_g = cand_of(k);
         } else {
           need = true;
         }
       }
-      if (h == 0 && row_valid) {  // a consumer issues no load: its stores need no fixed count
+      // (the row id is looked up here, not before the bound: nothing lives through the bound that need not)
+      const int lr = 32 * c + lane_now();
+      if (lr < min(32 * c + 32, D.nrows)) {  // lanes 0..31, one per row; a consumer issues no load: no fixed count
+        const int my_row = p.row_index ? reinterpret_cast<const int*>(hb + L::kHRow)[lr] : D.t0 + lr;
+        w.row = my_row;
+        w.seg = D.s;
         p.out_local[my_row] = out_l;
         p.out_global[my_row] = out_g;
         if (need) p.work[my_row] = w;
-        if (RL == 1 && NORM) p.den_out[my_row] = reinterpret_cast<const float*>(smem + L::kCoef + lr * 16)[2];
+        if (RL == 1 && NORM) p.den_out[my_row] = reinterpret_cast<const float*>(smem + L::kCoef + L::kCoefDen)[lr];
       }
       PST(s_eD += PNOW() - e0;)
     };
@@ -324,6 +400,9 @@ __global__ __launch_bounds__(768, 3) void assign_pc_kernel(AssignParams p, const
       atomicAdd(&g_pc_stamps[6], (unsigned long long)s_eU);
       atomicAdd(&g_pc_stamps[7], (unsigned long long)s_eB);
       atomicAdd(&g_pc_stamps[23], (unsigned long long)s_eD);
+      atomicAdd(&g_pc_stamps[15], (unsigned long long)s_g1);
+      atomicAdd(&g_pc_stamps[19], (unsigned long long)s_g2);
+      atomicAdd(&g_pc_stamps[21], (unsigned long long)s_g3);
     }
 #endif
     return;
@@ -424,7 +503,11 @@ __global__ __launch_bounds__(768, 3) void assign_pc_kernel(AssignParams p, const
       const float C = T3 ? k2 * ((en + en2) + ar * hn + ar2 * (hn + en + en2)) : 0.0f;
       const float m2 = -2.0f * inv_den * tscale;
       const float A2 = (A + B * (T3 ? tgz : tgw) + C * tgw + 2.39e-7f * tgy) * 1.000001f;
-      if (h == 0) *reinterpret_cast<float4*>(smem + L::kCoef + lr * 16) = make_float4(m2, A2, den, 0.f);
+      if (h == 0) {
+        reinterpret_cast<float*>(smem + L::kCoef)[lr] = m2;
+        reinterpret_cast<float*>(smem + L::kCoef + L::kCoefA2)[lr] = A2;
+        reinterpret_cast<float*>(smem + L::kCoef + L::kCoefDen)[lr] = den;
+      }
     };
 
     PcDesc Dc = load_desc(desc + T0);
