@@ -57,6 +57,14 @@ SIGNATURES = {
                                c_vp, c_vp, c_i32, c_vp, c_vp, c_vp,
                                c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                c_vp, c_vp, c_i32, c_vp, c_i64, c_vp]),
+    "rqsid_pair_table_bytes": (c_i64, [c_i32]),
+    "rqsid_pair_table": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp]),
+    "rqsid_assign_pair": (c_i32, [c_vp, c_i32, c_i64, c_i32, c_vp, c_i32, c_vp, c_vp, c_i64,
+                                  c_vp, c_vp, c_vp, c_vp, c_i32,
+                                  c_vp, c_vp, c_i32, c_vp, c_vp, c_vp,
+                                  c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                  c_vp, c_vp, c_i32, c_vp, c_i64, c_vp, c_vp]),
+    "rqsid_assign_plan_pair": (c_i32, [c_i32, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32]),
     "rqsid_assign_topk_workspace_bytes": (c_i64, [c_i64, c_i32]),
     "rqsid_assign_topk": (c_i32, [c_vp, c_i32, c_i64, c_i32, c_vp, c_i32, c_vp, c_vp, c_i64,
                                   c_vp, c_vp, c_i32,

@@ -96,6 +96,54 @@ __global__ void centers_scale_kernel(float* __restrict__ scale) {
 }
 
 // ---------------------------------------------------------------------------
+// pair table (the 2-term pairwise screen's |c_j - c_k|)
+// ---------------------------------------------------------------------------
+// T[seg][j][.]: for list positions j, k < cand_count[seg] (<= kPairCand) of segment seg, an fp16 >= |c_j - c_k|
+// 2^(s-7) (2^-s = the centre table's scale, meta[n_centers].x after rqsid_prepare_centers: the largest scaled
+// element is below 2^14 and dim <= kMaxDim, so the largest entry is below 2^14): fp64 from the fp32 centres,
+// widened by 1e-12 (the fp64 sum's own rounding), rounded UP to fp16 and, where positive, to no less than the
+// least normal fp16 (the screen runs with fp16 denormals flushed); inf for a non-finite distance or a candidate
+// index outside the table; 0 for positions past the list.  Entry k of row (seg, j) sits where the per-tile
+// screen's lane half h = (k >> 2) & 1 finds its 64 candidates in accumulator order (C/D registers t = k >> 5,
+// v = (k & 3) + 4 ((k & 31) >> 3)): at h 64 + t 16 + v, so a lane's slice is 128 consecutive bytes.
+// One block per (seg, j), a wave per k.
+__global__ __launch_bounds__(256) void pair_table_kernel(const float* __restrict__ c, int dim, const float* __restrict__ meta,
+                                                         int n_centers, const int32_t* __restrict__ cand_base,
+                                                         const int32_t* __restrict__ cand_count,
+                                                         const int32_t* __restrict__ cand_idx, _Float16* __restrict__ T) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int seg = blockIdx.x / kPairCand, j = blockIdx.x % kPairCand;
+  const int cnt = min(cand_count[seg], kPairCand), base = cand_base[seg];
+  _Float16* out = T + (int64_t)blockIdx.x * kPairCand;
+  const double unit = 1.0 / (128.0 * (double)meta[4 * (int64_t)n_centers]);  // 2^(s-7)
+  const int gj = j < cnt ? (cand_idx ? cand_idx[base + j] : base + j) : -1;
+  for (int k = wave; k < kPairCand; k += 4) {
+    _Float16 hv = (_Float16)0.0f;
+    if (j < cnt && k < cnt) {
+      const int gk = cand_idx ? cand_idx[base + k] : base + k;
+      hv = __builtin_bit_cast(_Float16, (uint16_t)0x7C00);  // inf
+      if ((unsigned)gj < (unsigned)n_centers && (unsigned)gk < (unsigned)n_centers) {
+        const float* cj = c + (int64_t)gj * dim;
+        const float* ck = c + (int64_t)gk * dim;
+        double s = 0.0;
+        for (int i = lane; i < dim; i += 64) {
+          const double d = (double)cj[i] - (double)ck[i];
+          s = fma(d, d, s);
+        }
+        const double x = sqrt(wave_sum(s)) * unit * (1.0 + 1e-12);
+        if (x < 65504.0) {  // (false for a NaN)
+          uint16_t b = __builtin_bit_cast(uint16_t, (_Float16)(float)x);
+          if ((double)(float)__builtin_bit_cast(_Float16, b) < x) ++b;  // next fp16 up (65504 -> inf)
+          if (x > 0.0 && b < 0x0400) b = 0x0400;                        // least normal
+          hv = __builtin_bit_cast(_Float16, b);
+        }
+      }
+    }
+    if (lane == 0) out[((k >> 2) & 1) * 64 + (k >> 5) * 16 + (k & 3) + 4 * ((k & 31) >> 3)] = hv;
+  }
+}
+
+// ---------------------------------------------------------------------------
 // screening kernel
 // ---------------------------------------------------------------------------
 #ifndef RQSID_INTERLEAVE  // 1: the ring's DMA ops interleaved with the MFMAs of the compute phase
@@ -212,6 +260,30 @@ __device__ __forceinline__ bool pass_decide_cw(const uint32_t (&pbits)[NW], int 
 // vh.ch (acc) and vl.ch + vh.cl (accl, its own accumulator) and the omitted vl.cl, (vh + vl).ec and
 // ev.c terms plus both accumulations are charged per candidate against |c|, |ec2| = |c - (ch + cl
 // 2^-12) 2^-s| and |ec1| = |c - ch 2^-s| (see the epilogue's A, B, C).
+// Two-term pairwise screen (PAIR: the single-pass fp32-row build over the 3-term centre image, <= kPairCand
+// candidates).  Rows go in as vh alone: v = vh + ex, and the MFMAs sum vh.ch (acc) and vh.cl (accl, units of
+// 2^-12), one instruction per accumulator and k-step.  With S_k the reference's |c_k|^2 - 2 r.c_k and P_k what
+// the epilogue computes, S_k - P_k = -2/den ex.c_k + g_k, so for two candidates of one row
+//   S_k - S_b = (P_k - P_b) - 2/den ex.(c_k - c_b) + g_k - g_b.
+//  * Row rounding, pairwise: |ex.(c_k - c_b)| <= |ex| |c_k - c_b| (Cauchy-Schwarz on the DIFFERENCE: centres
+//    that a row cannot tell apart lie close together, so this is far below |ex| (|c_k| + |c_b|)).  |c_j - c_k|
+//    comes from the pair table T (rqsid_pair_table: fp64 from the fp32 centres, rounded UP to fp16 in units of
+//    2^(7-s), never subnormal; >= the true distance, inf when that is not finite), |ex| is measured (en).
+//  * g_k, global as in the 3-term bound, |g_k| <= Ag |c_k| + Bg |ec2_k| + Cg |ec1_k| + e0_k:
+//      cl's own fp16 rounding     vh.ec2                   <= |vh| |ec2_k|
+//      acc's accumulation         acc_rel |vh| |ch_k|      <= acc_rel |vh| (|c_k| + |ec1_k|)
+//      accl's accumulation        acc_rel |vh| |cl_k 2^-12| <= acc_rel |vh| (|ec1_k| + |ec2_k|)
+//        (dim/16 chained instructions each, so acc_rel for both: the 3-term accl chains twice as many)
+//      dr, the fp32 epilogue      2 dr |c_k| + 7.2e-7 |r| |c_k| + e0_k, as in the 3-term screen
+//    i.e. Ag = 2/den acc_rel |vh| + 2 dr + 7.2e-7 |r|, Bg = 2/den |vh| (1 + acc_rel), Cg = 2/den |vh| 2 acc_rel,
+//    collapsed onto |c_k| with the tile constants of the single-pass epilogue below (A2).
+// With b = argmin P (lowest index), candidate k is dropped iff
+//   P_k - P_b > Ax T[b][k] + A2 (|c_k| + |c_b|) + 2e-30,   Ax = 2/den |ex|,
+// which implies S_k > S_b strictly: the exact argmin and every exact tie with it stay (b itself: 0 > positive
+// is false).  Ax and A2 carry a factor 1 + 1e-6 that covers the roundings of the threshold and of P_k - P_b
+// (three operations, 2^-24 each).  A non-finite bound or Pb (a NaN / Inf row, a value beyond fp16) passes every
+// candidate, an infinite T entry passes that candidate: "every candidate" for the re-screen and re-score.
+// Pass words, pass_decide, work lists and the re-score are those of the 3-term screen.
 // Single-pass epilogue (ONE: every segment has <= NT*32 candidates).  The per-candidate centre terms
 // collapse onto |c_k| with tile constants: |ec_k| <= gz |c_k|, |ec1_k| <= gw |c_k| (gz, gw = the largest
 // ratios over the tile's candidates, rounded up) and e0_k <= 2^-22 |c_k| ymax + 1e-30, so
@@ -235,10 +307,12 @@ __device__ unsigned long long g_stamps_tile[8];
 // image alone (ScreenLayout::kXS, the DMA op count in P, the LDS read) and widen each row element to fp32
 // right after the LDS read (widen2), so row_frag and everything after it run the fp32 build's operation
 // sequence on the same values: the bound argument is unchanged.
-template <int NT, int S, int RL, bool NORM, bool T3, bool ONE, int CW, int XF>
+template <int NT, int S, int RL, bool NORM, bool T3, bool ONE, int CW, int XF, bool PAIR = false>
 __device__ __forceinline__ void screen_tile(const AssignParams& p) {
   static_assert(CW == 1 || (ONE && (CW == 2 || CW == 4)), "candidate-split form: single-pass segments");
   static_assert(XF == RQSID_X_F32 || CW == 1, "16-bit rows: per-tile form only");
+  static_assert(!PAIR || (T3 && ONE && CW == 1 && NT == kPairCand / 32 && XF == RQSID_X_F32),
+                "2-term pairwise form: single-pass fp32-row build over the 3-term centre image");
   using L = ScreenLayout<NT, S, T3, CW, XF>;
   constexpr bool X16 = XF != RQSID_X_F32;
   constexpr int kXW = x_wave_bytes(XF);       // a wave's row image per stage
@@ -468,9 +542,9 @@ __device__ __forceinline__ void screen_tile(const AssignParams& p) {
           xc = *reinterpret_cast<const float4*>(xb + (((q0 + 1) ^ xsw) << 4));
         }
         const int d0 = c * kChunk + 16 * ks + 8 * h;
-        f16x8 bf, bl = {};
-        if (pass == 0) row_frag<RL, NORM, T3, true>(xa, xc, lds_ca, lds_cb, d0, inv1, bf, bl, rs);
-        else row_frag<RL, NORM, T3, false>(xa, xc, lds_ca, lds_cb, d0, inv1, bf, bl, rs);
+        f16x8 bf, bl = {};  // PAIR: rows hi only (no bl, no se2l)
+        if (pass == 0) row_frag<RL, NORM, T3 && !PAIR, true>(xa, xc, lds_ca, lds_cb, d0, inv1, bf, bl, rs);
+        else row_frag<RL, NORM, T3 && !PAIR, false>(xa, xc, lds_ca, lds_cb, d0, inv1, bf, bl, rs);
         const int qa = T3 ? (2 * ks + h) ^ tsw : (2 * ks + h) ^ csw;
         const int ql = (4 + 2 * ks + h) ^ tsw;
 #pragma unroll
@@ -484,7 +558,7 @@ __device__ __forceinline__ void screen_tile(const AssignParams& p) {
           if (T3) {
 #endif
             const f16x8 al = *reinterpret_cast<const f16x8*>(cbp + t * 32 * 128 + (ql << 4));
-            accl[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af, bl, accl[t], 0, 0, 0);
+            if (!PAIR) accl[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af, bl, accl[t], 0, 0, 0);
             accl[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bf, accl[t], 0, 0, 0);
           }
 #if RQSID_INTERLEAVE
@@ -527,7 +601,7 @@ __device__ __forceinline__ void screen_tile(const AssignParams& p) {
       const float se2 = rs.se2v.x + rs.se2v.y, sf2 = rs.sf2v.x + rs.sf2v.y;
       const float e2 = se2 + __shfl_xor(se2, 32);
       en = sqrtf(e2) * 1.001f + 1e-30f;
-      if (T3) {
+      if (T3 && !PAIR) {
         const float l2 = rs.se2l.x + rs.se2l.y;
         en2 = sqrtf(l2 + __shfl_xor(l2, 32)) * (1.001f / 4096.0f) + 1e-30f;
       }
@@ -587,6 +661,89 @@ __device__ __forceinline__ void screen_tile(const AssignParams& p) {
         gz = fmaxf(gz, m_red[w * 4 + 0]);
         gw = fmaxf(gw, m_red[w * 4 + 1]);
         gy = fmaxf(gy, m_red[w * 4 + 2]);
+      }
+      if constexpr (PAIR) {
+        // the global remainder (header comment, "Two-term pairwise screen"): against |c_k|, |ec2_k|, |ec1_k|
+        const float Ag = k2 * (ar * hn) + 2.0f * dr + 7.2e-7f * vr;
+        const float Bg = k2 * hn * (1.0f + ar);
+        const float Cg = k2 * hn * (2.0f * ar);
+        const float A2 = (Ag + Bg * gz + Cg * gw + 2.39e-7f * gy) * 1.000001f;
+        // against T[b][k] >= |c_k - c_b| 2^(s-7) (the table's unit is a power of two: exact)
+        const float Ax = k2 * en * 1.000001f * 128.0f *
+                         __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(p.c_meta[4 * p.n_centers])));
+        const f2 m2v = {m2, m2};
+        // sweep 1: P per candidate (kept in the accumulator), Pb = the least of them
+        float Pb = INFINITY;
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+          __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+          for (int g = 0; g < 4; ++g) {
+            const float4 cs = *reinterpret_cast<const float4*>(m_csq + t * 32 + 8 * g + 4 * h);
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+              const int v = 4 * g + 2 * e;
+              const f2 d = f2{accl[t][v], accl[t][v + 1]} * 0x1p-12f + f2{acc[t][v], acc[t][v + 1]};
+              const f2 P = m2v * d + (e ? f2{cs.z, cs.w} : f2{cs.x, cs.y});
+              Pb = fminf(Pb, fminf(P.x, P.y));
+              acc[t][v] = P.x;
+              acc[t][v + 1] = P.y;
+            }
+          }
+        }
+        Pb = fminf(Pb, __shfl_xor(Pb, 32));
+        // b = the lowest candidate with P == Pb: Pb - P is +0 there and negative elsewhere (pass-word order)
+        const f2 pbv = {Pb, Pb};
+        uint32_t eq[NT / 2];
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+          uint32_t b = (t & 1) ? eq[t >> 1] : 0u;
+#pragma unroll
+          for (int v = 0; v < 16; v += 2) {
+            const f2 d = pbv - f2{acc[t][v], acc[t][v + 1]};
+            b = __builtin_amdgcn_alignbit(b, __float_as_uint(d.x), 31);
+            b = __builtin_amdgcn_alignbit(b, __float_as_uint(d.y), 31);
+          }
+          eq[t >> 1] = b;
+        }
+#pragma unroll
+        for (int w = 0; w < NT / 2; ++w) eq[w] = ~eq[w];
+        const int kb = pass_take_first(eq, h), kb_o = __shfl_xor(kb, 32);
+        // (neither half finds one only in a row of NaNs, which ends as "every candidate" below: any row will do)
+        const int bi = (kb >= 0 && kb_o >= 0 ? min(kb, kb_o) : max(kb, kb_o)) & (kPairCand - 1);
+        // this half's 64 entries of T[s][bi][.], in accumulator order: one dependent L2 read per tile
+        const uint4* tp = reinterpret_cast<const uint4*>(p.pair) + ((int64_t)s * kPairCand + bi) * (kPairCand / 8) + h * (2 * NT);
+        uint4 tw[2 * NT];
+#pragma unroll
+        for (int j = 0; j < 2 * NT; ++j) tw[j] = tp[j];
+        const float eb = fmaf(A2, m_y[bi], 2e-30f);
+        // a non-finite row (or bound): every candidate, whatever the signs of the NaNs below
+        const bool finite = A2 + Ax < INFINITY && fabsf(Pb) < INFINITY;
+        const f2 a2v = {A2, A2}, axv = {Ax, Ax}, ebv = {eb, eb};
+        // sweep 2: candidate k stays unless P_k - P_b > Ax T[b][k] + A2 (|c_k| + |c_b|) + 2e-30, i.e. the pass
+        // bit is the sign of (P_k - P_b) - threshold
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+          __builtin_amdgcn_sched_barrier(0);
+          uint32_t b = (t & 1) ? pbits[t >> 1] : 0u;
+#pragma unroll
+          for (int g = 0; g < 4; ++g) {
+            const float4 yy = *reinterpret_cast<const float4*>(m_y + t * 32 + 8 * g + 4 * h);
+            const uint4 tq = tw[2 * t + (g >> 1)];
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+              const int v = 4 * g + 2 * e;
+              const uint32_t tb = (g & 1) ? (e ? tq.w : tq.z) : (e ? tq.y : tq.x);
+              const f2 T = __builtin_convertvector(__builtin_bit_cast(h2, tb), f2);
+              const f2 thr = axv * T + (a2v * (e ? f2{yy.z, yy.w} : f2{yy.x, yy.y}) + ebv);
+              const f2 d = (f2{acc[t][v], acc[t][v + 1]} - pbv) - thr;
+              b = __builtin_amdgcn_alignbit(b, __float_as_uint(d.x), 31);
+              b = __builtin_amdgcn_alignbit(b, __float_as_uint(d.y), 31);
+            }
+          }
+          pbits[t >> 1] = finite ? b : 0xFFFFFFFFu;
+        }
+        continue;  // npass == 1
       }
       const float A2 = (A + B * gz + C * gw + 2.39e-7f * gy) * 1.000001f;
       const f2 m2v = {m2, m2}, a2v = {A2, A2}, epsv = {1e-30f, 1e-30f};
@@ -782,6 +939,11 @@ constexpr int screen_min_blocks(int NT, int S, bool T3, int CW) {
 template <int NT, int S, int RL, bool NORM, bool T3, bool ONE, int CW = 1>
 __global__ __launch_bounds__(256 * CW, screen_min_blocks(NT, S, T3, CW)) void assign_screen_kernel(AssignParams p) {
   screen_tile<NT, S, RL, NORM, T3, ONE, CW, RQSID_X_F32>(p);
+}
+// the 2-term pairwise form of assign_screen_kernel<4, 2, RL, NORM, true, true, 1> (needs AssignParams::pair)
+template <int RL, bool NORM>
+__global__ __launch_bounds__(256, screen_min_blocks(4, 2, true, 1)) void assign_screen_pair_kernel(AssignParams p) {
+  screen_tile<4, 2, RL, NORM, true, true, 1, RQSID_X_F32, true>(p);
 }
 // 16-bit rows (XF = RQSID_X_F16 / RQSID_X_BF16): rqsid_assign_x
 template <int XF, int NT, int S, int RL, bool NORM, bool T3, bool ONE>
@@ -1227,6 +1389,13 @@ int ensure_attrs() {
   set_attrs_xf<RQSID_X_BF16>(&ok);
   set_attrs<8, kSplitS, false, true, 2>(&ok);  // the candidate split: fp32 rows only
   set_attrs<4, kSplitS, true, true, 2>(&ok);
+  for (int rl = 0; rl <= 2; ++rl)  // the 2-term pairwise form's five builds
+    for (int norm = 0; norm <= (rl ? 1 : 0); ++norm)
+      dispatch_rl_norm(rl, norm != 0, [&](auto RL, auto NORM) {
+        if (hipFuncSetAttribute((const void*)assign_screen_pair_kernel<RL(), NORM()>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                ScreenLayout<4, 2, true>::kMaxBytes) != hipSuccess)
+          ok = false;
+      });
   if (!ok) return fail(RQSID_E_LAUNCH, "assign: cannot raise the dynamic LDS limit");
   g_attr_done[dev] = true;
   return RQSID_OK;
@@ -1248,6 +1417,13 @@ void launch_screen2(const AssignParams& p, int rl, bool norm, unsigned grid, boo
 template <int XF>
 void launch_tile_screen(const AssignParams& p, const AssignPlan& plan, int rl, bool norm, unsigned grid, hipStream_t st) {
   if constexpr (XF == RQSID_X_F32) {
+    if (plan.pair) {
+      const size_t lds = ScreenLayout<4, 2, true>::bytes(rl, p.dim);
+      dispatch_rl_norm(rl, norm, [&](auto RL, auto NORM) {
+        hipLaunchKernelGGL((assign_screen_pair_kernel<RL(), NORM()>), dim3(grid), dim3(256), lds, st, p);
+      });
+      return;
+    }
     if (plan.cw == 2 && plan.t3) return launch_screen<4, kSplitS, true, true, 2>(p, rl, norm, grid, st);
     if (plan.cw == 2) return launch_screen<8, kSplitS, false, true, 2>(p, rl, norm, grid, st);
   }
@@ -1304,6 +1480,7 @@ AssignEnv read_assign_env() {
   e.rows_shape = env_int("RQSID_ROWS_SHAPE", e.rows_shape);
   e.rescore_full = env_int("RQSID_RESCORE_FULL", e.rescore_full);
   e.no_rescreen = env_int("RQSID_NO_RESCREEN", e.no_rescreen);
+  e.no_pair = env_int("RQSID_NO_PAIR", e.no_pair);
   e.test_force_spin_cap = env_int("RQSID_TEST_FORCE_SPIN_CAP", e.test_force_spin_cap);
   return e;
 }
@@ -1348,7 +1525,8 @@ int32_t rqsid_assign_tile_rows(void) { return kTileRows; }
 // (the workspace's areas: AssignWorkspaceMap, assign_plan.h)
 int64_t rqsid_assign_workspace_bytes(int64_t n_rows) { return AssignWorkspaceMap(n_rows).total_bytes; }
 
-int rqsid_assign_x(const void* x, int32_t x_format, int64_t n_rows, int32_t dim, const int32_t* row_index, int32_t n_segments,
+// rqsid_assign_x / rqsid_assign_pair: pair_table NULL or the segments' pair table (rqsid_pair_table)
+static int assign_call(const void* x, int32_t x_format, int64_t n_rows, int32_t dim, const int32_t* row_index, int32_t n_segments,
                  const int32_t* seg_row_off, const int32_t* seg_tile_off, int64_t max_tiles, const float* centers,
                  const uint16_t* c16, const uint16_t* c16_hi, const float* c_meta, int32_t n_centers,
                  const int32_t* cand_base,
@@ -1356,7 +1534,11 @@ int rqsid_assign_x(const void* x, int32_t x_format, int64_t n_rows, int32_t dim,
                  const int32_t* cand_lid, const uint8_t* seg_flags, int32_t res_levels, int32_t res_normalize, const float* ca,
                  const int32_t* seg_ca, const float* cb, const int32_t* seg_cb, const float* den_in,
                  float* den_out, int32_t* out_local, int32_t* out_global, int32_t screen_terms, void* workspace,
-                 int64_t workspace_bytes, void* stream) {
+                 int64_t workspace_bytes, void* stream, const uint16_t* pair_table) {
+  if (screen_terms == 2 && !pair_table)
+    return fail(RQSID_E_ARG, "assign: screen_terms = 2 needs a pair table (rqsid_assign_pair)");
+  if (pair_table && (reinterpret_cast<uintptr_t>(pair_table) & 15))
+    return fail(RQSID_E_ARG, "assign: the pair table must be 16-byte aligned");
   if (x_format != RQSID_X_F32 && x_format != RQSID_X_F16 && x_format != RQSID_X_BF16)
     return fail(RQSID_E_ARG, "assign: unknown x_format %d (RQSID_X_F32, RQSID_X_F16, RQSID_X_BF16)", x_format);
   const bool x16 = x_format != RQSID_X_F32;
@@ -1365,7 +1547,7 @@ int rqsid_assign_x(const void* x, int32_t x_format, int64_t n_rows, int32_t dim,
   if (dim <= 0 || dim % kChunk || dim > kMaxDim || n_rows < 0 || n_segments <= 0 || !seg_row_off ||
       !seg_tile_off || !centers || !c16 || !c_meta || !cand_base || !cand_count || (n_rows > 0 && (!out_local || !out_global)) ||
       n_centers <= 0 || cand_count_max < 0 || max_tiles < 0 || n_rows > INT32_MAX || res_levels < 0 ||
-      res_levels > 2 || (screen_terms != 0 && screen_terms != 1 && screen_terms != 3))
+      res_levels > 2 || screen_terms < 0 || screen_terms > 3)
     return fail(RQSID_E_ARG, "assign: bad arguments (n=%lld dim=%d S=%d K=%d levels=%d)", (long long)n_rows, dim,
                 n_segments, n_centers, res_levels);
   if ((res_levels >= 1 && !ca) || (res_levels == 2 && (!cb || !seg_cb || (res_normalize && n_rows > 0 && !den_in))))
@@ -1390,6 +1572,7 @@ int rqsid_assign_x(const void* x, int32_t x_format, int64_t n_rows, int32_t dim,
   shape.screen_terms = screen_terms;
   shape.has_cand_lid = cand_lid != nullptr;
   shape.has_den_out = den_out != nullptr;
+  shape.has_pair = pair_table != nullptr;
   const AssignPlan plan = plan_assign(shape, read_assign_env());
 
   const AssignWorkspace ws(n_rows, workspace);
@@ -1417,13 +1600,14 @@ int rqsid_assign_x(const void* x, int32_t x_format, int64_t n_rows, int32_t dim,
   p.work_cap = n_rows;
   p.work_idx = nullptr;
   p.acc_rel = accumulation_rel(dim);
-  p.terms = plan.t3 ? 3 : 1;
+  p.terms = plan.pair ? 2 : plan.t3 ? 3 : 1;
   p.ca = ca;
   p.seg_ca = seg_ca;
   p.cb = cb;
   p.seg_cb = seg_cb;
   p.den_in = den_in;
   p.den_out = den_out;
+  p.pair = pair_table;
   // header ints [0, 60) per call; [60, 64) hold the sticky error word (kErrSlot), zeroed by the allocator
   if (fill_async(workspace, 0, 4 * kErrSlot, st) != hipSuccess) return fail(RQSID_E_LAUNCH, "assign: memset");
 
@@ -1491,6 +1675,71 @@ int rqsid_assign_x(const void* x, int32_t x_format, int64_t n_rows, int32_t dim,
     if (err) return fail(RQSID_E_LAUNCH, "assign: a resident-screen wait reached its spin cap (error word %d)", err);
   }
   return RQSID_OK;
+}
+
+int rqsid_assign_x(const void* x, int32_t x_format, int64_t n_rows, int32_t dim, const int32_t* row_index, int32_t n_segments,
+                 const int32_t* seg_row_off, const int32_t* seg_tile_off, int64_t max_tiles, const float* centers,
+                 const uint16_t* c16, const uint16_t* c16_hi, const float* c_meta, int32_t n_centers,
+                 const int32_t* cand_base,
+                 const int32_t* cand_count, int32_t cand_count_max, const int32_t* cand_idx,
+                 const int32_t* cand_lid, const uint8_t* seg_flags, int32_t res_levels, int32_t res_normalize, const float* ca,
+                 const int32_t* seg_ca, const float* cb, const int32_t* seg_cb, const float* den_in,
+                 float* den_out, int32_t* out_local, int32_t* out_global, int32_t screen_terms, void* workspace,
+                 int64_t workspace_bytes, void* stream) {
+  return assign_call(x, x_format, n_rows, dim, row_index, n_segments, seg_row_off, seg_tile_off, max_tiles, centers,
+                     c16, c16_hi, c_meta, n_centers, cand_base, cand_count, cand_count_max, cand_idx, cand_lid, seg_flags,
+                     res_levels, res_normalize, ca, seg_ca, cb, seg_cb, den_in, den_out, out_local, out_global,
+                     screen_terms, workspace, workspace_bytes, stream, nullptr);
+}
+
+int rqsid_assign_pair(const void* x, int32_t x_format, int64_t n_rows, int32_t dim, const int32_t* row_index, int32_t n_segments,
+                 const int32_t* seg_row_off, const int32_t* seg_tile_off, int64_t max_tiles, const float* centers,
+                 const uint16_t* c16, const uint16_t* c16_hi, const float* c_meta, int32_t n_centers,
+                 const int32_t* cand_base,
+                 const int32_t* cand_count, int32_t cand_count_max, const int32_t* cand_idx,
+                 const int32_t* cand_lid, const uint8_t* seg_flags, int32_t res_levels, int32_t res_normalize, const float* ca,
+                 const int32_t* seg_ca, const float* cb, const int32_t* seg_cb, const float* den_in,
+                 float* den_out, int32_t* out_local, int32_t* out_global, int32_t screen_terms, void* workspace,
+                 int64_t workspace_bytes, void* stream, const uint16_t* pair_table) {
+  return assign_call(x, x_format, n_rows, dim, row_index, n_segments, seg_row_off, seg_tile_off, max_tiles, centers,
+                     c16, c16_hi, c_meta, n_centers, cand_base, cand_count, cand_count_max, cand_idx, cand_lid, seg_flags,
+                     res_levels, res_normalize, ca, seg_ca, cb, seg_cb, den_in, den_out, out_local, out_global,
+                     screen_terms, workspace, workspace_bytes, stream, pair_table);
+}
+
+int32_t rqsid_assign_plan_pair(int32_t x_format, int64_t n_rows, int32_t dim, int32_t n_segments, int32_t cand_count_max,
+                               int32_t res_levels, int32_t res_normalize, int32_t screen_terms, int32_t has_cand_lid,
+                               int32_t has_den_out, int32_t has_pair) {
+  AssignShape shape;
+  shape.x_format = x_format;
+  shape.n_rows = n_rows;
+  shape.dim = dim;
+  shape.n_segments = n_segments;
+  shape.cand_count_max = cand_count_max;
+  shape.res_levels = res_levels;
+  shape.norm = res_normalize != 0;
+  shape.screen_terms = screen_terms;
+  shape.has_cand_lid = has_cand_lid != 0;
+  shape.has_den_out = has_den_out != 0;
+  shape.has_pair = has_pair != 0;
+  return plan_assign(shape, read_assign_env()).pair ? 1 : 0;
+}
+
+int64_t rqsid_pair_table_bytes(int32_t n_segments) {
+  return (int64_t)(n_segments > 0 ? n_segments : 0) * kPairCand * kPairCand * 2;
+}
+
+int rqsid_pair_table(const float* centers, int32_t dim, const float* c_meta, int32_t n_centers, int32_t n_segments,
+                     const int32_t* cand_base, const int32_t* cand_count, int32_t cand_count_max, const int32_t* cand_idx,
+                     uint16_t* pair_table, void* stream) {
+  if (!centers || !c_meta || !cand_base || !cand_count || !pair_table || dim <= 0 || dim % kChunk || dim > kMaxDim ||
+      n_centers <= 0 || n_segments <= 0 || n_segments > INT32_MAX / kPairCand || cand_count_max < 0 ||
+      cand_count_max > kPairCand || (reinterpret_cast<uintptr_t>(pair_table) & 15))
+    return fail(RQSID_E_ARG, "pair_table: bad arguments (dim=%d S=%d K=%d cand_count_max=%d; at most %d candidates per segment)",
+                dim, n_segments, n_centers, cand_count_max, kPairCand);
+  hipLaunchKernelGGL(pair_table_kernel, dim3((unsigned)n_segments * kPairCand), dim3(256), 0, (hipStream_t)stream, centers,
+                     dim, c_meta, n_centers, cand_base, cand_count, cand_idx, reinterpret_cast<_Float16*>(pair_table));
+  return check_launch("pair_table");
 }
 
 int rqsid_assign(const float* x, int64_t n_rows, int32_t dim, const int32_t* row_index, int32_t n_segments,

@@ -38,6 +38,8 @@ constexpr int x_stage_bytes(int xf) { return kWaves * x_wave_bytes(xf); }
 constexpr int x_wave_ops(int xf) { return x_wave_bytes(xf) / 1024; }  // 1-KiB DMA ops per wave per chunk
 static_assert(x_wave_bytes(RQSID_X_F32) == kXWaveBytes && x_stage_bytes(RQSID_X_F32) == kXStage, "fp32 row image");
 
+constexpr int kPairCand = 128;              // candidates per segment of the pair table (rqsid_pair_table)
+static_assert(kPairCand == kPlanPairCand, "assign_plan.h constants");
 constexpr int kListPerHalf = 4;             // candidates a lane half can list exactly
 constexpr int kMaxList = 2 * kListPerHalf;   // per row
 struct WorkItem {
@@ -75,7 +77,7 @@ struct AssignParams {
   const int32_t* tile_seg;  // tile -> segment (per-tile screen; NULL: binary search of seg_tile_off)
   int64_t work_cap;
   float acc_rel;
-  int32_t terms;          // 1 or 3 (screen product terms; host-side dispatch only)
+  int32_t terms;          // 1, 2 (the pairwise form) or 3 (screen product terms; host-side dispatch only)
   const float* ca;
   const int32_t* seg_ca;
   const float* cb;
@@ -84,6 +86,7 @@ struct AssignParams {
   float* den_out;
   int32_t* err;           // device error word (resident screen: bit 0 = a role wait reached its spin cap)
   int32_t force_cap;      // tests only: the resident screen's final wait takes a zero spin cap
+  const uint16_t* pair;   // NULL, or the pair table (rqsid_pair_table; the 2-term pairwise screen reads it)
 };
 
 __device__ __forceinline__ int cand_global(const AssignParams& p, int base, int local) {

@@ -20,6 +20,7 @@ constexpr int kPlanPcDescBytes = 32; // sizeof(PcDesc)
 constexpr int kPlanResDim = 512;     // kRD: the centre-resident screen's row width
 constexpr int kPlanRowsDim = 512;    // kRDim: the row-resident screen's row width
 constexpr int kPlanRowsMaxCand = 512;  // kRMaxCand
+constexpr int kPlanPairCand = 128;   // kPairCand: candidates per segment of the pair table
 constexpr int kPlanWorkItemBytes = 32;    // sizeof(WorkItem)
 constexpr int kPlanDescBytesPerRow = 16;  // the workspace's descriptor area: one int4 per row
 
@@ -64,9 +65,10 @@ struct AssignShape {
   int cand_count_max = 0;
   int res_levels = 0;
   bool norm = false;
-  int screen_terms = 0;  // 0 auto, 1, 3
+  int screen_terms = 0;  // 0 auto, 1, 2 (needs has_pair), 3
   bool has_cand_lid = false;
   bool has_den_out = false;
+  bool has_pair = false;  // the call brings a pair table (rqsid_pair_table): |c_j - c_k| per segment list
 };
 
 // every switch the assign path reads, with its default
@@ -84,13 +86,17 @@ struct AssignEnv {
   int rows_shape = 443;
   int rescore_full = 0;    // RQSID_RESCORE_FULL=1: one row per wave in the re-score (A/B)
   int no_rescreen = 0;     // RQSID_NO_RESCREEN=1: no fp32 re-screen (A/B)
+  int no_pair = 0;         // RQSID_NO_PAIR=1: the 3-term screen where the 2-term pairwise form would run (A/B)
   int test_force_spin_cap = 0;  // RQSID_TEST_FORCE_SPIN_CAP (tests only)
 };
 
 struct AssignPlan {
   enum Screen { kTile, kStream, kRows, kResident, kPc };
   Screen screen = kTile;
-  bool t3 = false;  // 3-term screen
+  bool t3 = false;  // 3-term screen (or its 2-term pairwise form: pair)
+  // per-tile screen, single pass, fp32 rows, <= 128 candidates: centres hi + lo, rows hi only, the row-rounding
+  // part of the bound charged pairwise through the call's pair table
+  bool pair = false;
   int nt = 4;       // MFMA candidate tiles per wave (tile, stream, pc)
   // per-tile screen only: single-pass epilogue, candidate groups (2: the candidate-split form), ring depth
   bool one = false;
@@ -136,7 +142,10 @@ inline int64_t pc_desc_bytes(int64_t n_rows, int32_t n_segments) {
 //  * Terms: the 3-term screen (rounding residuals of both operands summed by two more MFMAs) shrinks the
 //    bound ~5x at 2 blocks/CU; auto picks it for residual levels with <= 128 candidates, and for first
 //    residual levels of <= 256 (the XL preset's middle level: the 1-term bound leaves ~2/3 of those rows to
-//    the fp64 re-score).  The 8-tile form has no 3-term build (256 VGPRs).
+//    the fp64 re-score).  The 8-tile form has no 3-term build (256 VGPRs).  Where the per-tile single-pass
+//    3-term screen of fp32 rows would run and the call brings a pair table, its 2-term pairwise form runs
+//    instead (one MFMA of three dropped; screen_terms = 2 asks for it, RQSID_NO_PAIR=1 keeps 3 terms); a call
+//    that asks for 2 terms where that form does not apply gets the 3-term screen.
 //  * 16-bit rows take the per-tile form only, without the candidate split; variants that name another
 //    screen are ignored for them.
 //  * Defaults (variant 0): producer/consumer for the 1-term residual levels it covers (PROD level 2;
@@ -150,8 +159,9 @@ inline AssignPlan plan_assign(const AssignShape& a, const AssignEnv& e) {
   AssignPlan pl;
   const int ccm = a.cand_count_max, rl = a.res_levels, variant = e.screen_variant;
   const bool x16 = a.x_format != kPlanXF32;
-  const bool t3 = (ccm <= 128 && (a.screen_terms == 3 || (a.screen_terms == 0 && rl >= 1))) ||
-                  (ccm <= 256 && (a.screen_terms == 3 || (a.screen_terms == 0 && rl == 1)));
+  const bool want3 = a.screen_terms == 3 || a.screen_terms == 2;
+  const bool t3 = (ccm <= 128 && (want3 || (a.screen_terms == 0 && rl >= 1))) ||
+                  (ccm <= 256 && (want3 || (a.screen_terms == 0 && rl == 1)));
   const bool legacy = variant == 2;
   pl.t3 = t3;
   pl.nt = t3 || ccm <= 128 ? 4 : 8;
@@ -189,6 +199,7 @@ inline AssignPlan plan_assign(const AssignShape& a, const AssignEnv& e) {
     const int one_pass = pl.nt * 32;  // candidates one wave's tiles cover
     if (ccm <= one_pass) {
       pl.one = !legacy;
+      pl.pair = t3 && pl.one && !x16 && a.has_pair && !e.no_pair && a.screen_terms != 3;
     } else if (ccm <= 2 * one_pass && split) {
       pl.one = true;
       pl.cw = 2;

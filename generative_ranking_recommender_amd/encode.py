@@ -148,6 +148,10 @@ class RQEncoder:
             self.raw_cands.append(c)
             # bitwise-duplicate centres can never be the first minimum: drop them from the lists
             self.cands.append(ops.dedup_candidates(c, self.pcs[l].centers))
+        # middle levels: the pair table of the deduplicated lists (the 2-term pairwise screen; None where a list
+        # is wider than it covers), built once: codebook and lists are fixed for the encoder's life
+        self.pairs: List[Optional[torch.Tensor]] = [
+            ops.pair_table(self.pcs[l], self.cands[l]) if 0 < l < self.L - 1 else None for l in range(self.L)]
         self._ws = None
         self._bws = {}  # n_segments -> reusable rqsid_bucket workspace (sticky error word)
         self.last_rescored = []
@@ -416,7 +420,8 @@ class RQEncoder:
         glob1 = torch.empty(n, dtype=torch.int32, device=dev)
         b = self._bucket(out[0], self.need[0]) if self.L == 3 else self._last_level_buckets(out, 1, n, dev)
         fr1 = ops.FusedResidual(1, norm, self.pcs[0].centers, None, den_out=n1)
-        ops.assign(x, self.pcs[1], b, self.cands[1], out_local=out[1], out_global=glob1, workspace=ws, fused=fr1)
+        ops.assign(x, self.pcs[1], b, self.cands[1], out_local=out[1], out_global=glob1, workspace=ws, fused=fr1,
+                   pair=self.pairs[1])
         if tk is not None:
             tk.level(1, x, b, fr1)
         if count_rescored:
@@ -458,7 +463,8 @@ class RQEncoder:
                 out[0].copy_(glob)
             elif l < self.L - 1:
                 b = self._bucket(out[l - 1], self.need[l - 1])
-                ops.assign(w, self.pcs[l], b, self.cands[l], out_local=out[l], out_global=glob, workspace=ws)
+                ops.assign(w, self.pcs[l], b, self.cands[l], out_local=out[l], out_global=glob, workspace=ws,
+                           pair=self.pairs[l])
             else:
                 b = self._last_level_buckets(out, l, n, x.device)
                 ops.assign(w, self.pcs[l], b, self.cands[l], out_local=out[l], out_global=glob, workspace=ws)

@@ -267,13 +267,43 @@ class FusedResidual:
     den_out: Optional[torch.Tensor] = None
 
 
+PAIR_CAND = 128  # kPairCand: the widest segment list a pair table covers
+
+
+def pair_table(pc: PreparedCenters, cand: Candidates) -> Optional[torch.Tensor]:
+    """The pair table of a level's segment lists (rqsid_pair_table: fp16 upper bounds of |c_j - c_k| per list),
+    for ``assign(..., pair=...)``; None where a list is wider than PAIR_CAND.  Build it once per codebook and
+    candidate lists (after any dedup_candidates): 32 KiB per segment."""
+    if cand.count_max > PAIR_CAND or cand.count_max <= 0:
+        return None
+    _require_device(pc.centers, cand.base, cand.count, cand.idx)
+    n_seg = cand.base.numel()
+    t = torch.empty(int(lib().rqsid_pair_table_bytes(n_seg)) // 2, dtype=torch.int16, device=pc.centers.device)
+    _lib.check(lib().rqsid_pair_table(_ptr(pc.centers), pc.centers.shape[1], _ptr(pc.meta), pc.k, n_seg, _ptr(cand.base),
+                                      _ptr(cand.count), cand.count_max, _ptr(cand.idx), _ptr(t), _stream()),
+               "rqsid_pair_table")
+    return t
+
+
+def assign_plan_pair(x: torch.Tensor, buckets: Buckets, cand: Candidates, fused: Optional[FusedResidual] = None,
+                     screen_terms: int = 0, pair: Optional[torch.Tensor] = None) -> bool:
+    """True if ``assign`` with these arguments runs the 2-term pairwise screen (host-only query of the plan)."""
+    f = fused
+    return bool(lib().rqsid_assign_plan_pair(
+        ROW_FORMATS[x.dtype], x.shape[0], x.shape[1], buckets.n_segments, cand.count_max,
+        0 if f is None else f.levels, 0 if f is None else int(f.normalize), int(screen_terms),
+        int(cand.lid is not None), int(f is not None and f.den_out is not None), int(pair is not None)))
+
+
 def assign(x: torch.Tensor, pc: PreparedCenters, buckets: Buckets, cand: Candidates,
            out_local: Optional[torch.Tensor] = None, out_global: Optional[torch.Tensor] = None,
            workspace: Optional[AssignWorkspace] = None, fused: Optional[FusedResidual] = None,
-           screen_terms: int = 0):
-    """Exact segmented argmin. Returns (local i32[N], global i32[N]).  ``screen_terms`` (0 auto, 1, 3)
+           screen_terms: int = 0, pair: Optional[torch.Tensor] = None):
+    """Exact segmented argmin. Returns (local i32[N], global i32[N]).  ``screen_terms`` (0 auto, 1, 2, 3)
     only changes how much work the exact answer takes.  ``x``: float32, or float16 / bfloat16 rows, which
-    the kernels read as they are (rqsid_assign_x: no fp32 copy; IDs bit-identical to ``x.float()``)."""
+    the kernels read as they are (rqsid_assign_x: no fp32 copy; IDs bit-identical to ``x.float()``).
+    ``pair``: ``pair_table(pc, cand)`` of the same centres and lists; with it the 3-term levels of fp32 rows run
+    the 2-term pairwise screen (rqsid_assign_pair), and ``screen_terms=2`` asks for that form."""
     _require_device(x, pc.centers, cand.base, cand.count, cand.idx, cand.flags)
     x_format = ROW_FORMATS.get(x.dtype)
     if x_format is None:
@@ -291,8 +321,16 @@ def assign(x: torch.Tensor, pc: PreparedCenters, buckets: Buckets, cand: Candida
     f = fused
     if f is not None:
         _require_device(f.ca, f.seg_ca, f.cb, f.seg_cb, f.den_in, f.den_out)
-    fn, head, what = (lib().rqsid_assign, (), "rqsid_assign") if x_format == 0 else \
-        (lib().rqsid_assign_x, (x_format,), "rqsid_assign_x")
+    tail = ()
+    if pair is not None:
+        _require_device(pair)
+        if pair.numel() * pair.element_size() < int(lib().rqsid_pair_table_bytes(buckets.n_segments)):
+            raise ValueError("pair table smaller than rqsid_pair_table_bytes(n_segments)")
+        fn, head, tail, what = lib().rqsid_assign_pair, (x_format,), (_ptr(pair),), "rqsid_assign_pair"
+    elif x_format == 0:
+        fn, head, what = lib().rqsid_assign, (), "rqsid_assign"
+    else:
+        fn, head, what = lib().rqsid_assign_x, (x_format,), "rqsid_assign_x"
     _lib.check(fn(
         _ptr(x), *head, n, d, _ptr(buckets.row_index), buckets.n_segments, _ptr(buckets.seg_row_off),
         _ptr(buckets.seg_tile_off), buckets.max_tiles,
@@ -302,7 +340,7 @@ def assign(x: torch.Tensor, pc: PreparedCenters, buckets: Buckets, cand: Candida
         None if f is None else _ptr(f.ca), None if f is None else _ptr(f.seg_ca),
         None if f is None else _ptr(f.cb), None if f is None else _ptr(f.seg_cb),
         None if f is None else _ptr(f.den_in), None if f is None else _ptr(f.den_out),
-        _ptr(out_local), _ptr(out_global), int(screen_terms), _ptr(workspace.buf), workspace.bytes, _stream()),
+        _ptr(out_local), _ptr(out_global), int(screen_terms), _ptr(workspace.buf), workspace.bytes, _stream(), *tail),
         what)
     return out_local, out_global
 

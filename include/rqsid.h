@@ -116,8 +116,9 @@ int32_t rqsid_assign_tile_rows(void);
  * bound, then an fp64 re-score of every row whose bound admits more than one candidate.
  * screen_terms: 1 = vh.ch only; 3 = vh.ch + vl.ch + vh.cl (both operands' fp16 rounding
  * residuals, a ~5x tighter bound for 3x the MFMA work; segments of <= 128 candidates only, wider
- * ones use 1); 0 = automatic (3 for residual levels with <= 128 candidates per segment).  The result
- * never depends on it, only the speed.
+ * ones use 1); 0 = automatic (3 for residual levels with <= 128 candidates per segment); 2 = the 2-term
+ * pairwise form of rqsid_assign_pair (below; RQSID_E_ARG here, where no pair table comes with the call).  The
+ * result never depends on it, only the speed.
  *
  * Errors: RQSID_E_ARG / RQSID_E_WORKSPACE before any launch; RQSID_E_LAUNCH for a HIP launch failure
  * or, on the opt-in centre-resident screen (RQSID_SCREEN_VARIANT=6), when a wave's capped role wait
@@ -164,6 +165,39 @@ int rqsid_assign_x(const void* x, int32_t x_format, int64_t n_rows, int32_t dim,
                    const float* den_in, float* den_out,
                    int32_t* out_local, int32_t* out_global, int32_t screen_terms,
                    void* workspace, int64_t workspace_bytes, void* stream);
+
+/* Pair table of a level's segment lists, for rqsid_assign_pair: per segment s and list positions j, k <
+ * cand_count[s] (cand_count_max <= 128), an fp16 upper bound of |c_j - c_k| (fp64 from the fp32 centres, rounded
+ * up; in units of the centre table's scale, so build it after rqsid_prepare_centers of the same c_meta, and again
+ * whenever the centres or the lists change).  pair_table: rqsid_pair_table_bytes(n_segments) bytes (32 KiB per
+ * segment), 16-byte aligned; its layout is the screen's own. */
+int64_t rqsid_pair_table_bytes(int32_t n_segments);
+int rqsid_pair_table(const float* centers, int32_t dim, const float* c_meta, int32_t n_centers, int32_t n_segments,
+                     const int32_t* cand_base, const int32_t* cand_count, int32_t cand_count_max,
+                     const int32_t* cand_idx, uint16_t* pair_table, void* stream);
+/* rqsid_assign_x with an optional pair table (NULL: rqsid_assign_x itself).  With one, and where the per-tile
+ * single-pass 3-term screen of fp32 rows would run (segments of <= 128 candidates), its 2-term pairwise form
+ * runs instead: vh.ch + vh.cl, the rows' own fp16 rounding charged per candidate pair as |x - fp16(x)| |c_k -
+ * c_b| against the row's best candidate b.  One MFMA of three less; a few more rows reach the
+ * re-score; the IDs are the same.  screen_terms = 2 asks for this form (RQSID_E_ARG without a table; the 3-term
+ * screen where the form does not apply), 0 picks it wherever 3 terms would be picked, 3 and RQSID_NO_PAIR=1 keep
+ * the 3-term screen.  rqsid_assign_plan_pair: 1 if a call of that shape, under the current environment, runs
+ * the 2-term pairwise form. */
+int rqsid_assign_pair(const void* x, int32_t x_format, int64_t n_rows, int32_t dim, const int32_t* row_index,
+                      int32_t n_segments, const int32_t* seg_row_off, const int32_t* seg_tile_off,
+                      int64_t max_tiles,
+                      const float* centers, const uint16_t* c16, const uint16_t* c16_hi, const float* c_meta,
+                      int32_t n_centers,
+                      const int32_t* cand_base, const int32_t* cand_count, int32_t cand_count_max,
+                      const int32_t* cand_idx, const int32_t* cand_lid, const uint8_t* seg_flags,
+                      int32_t res_levels, int32_t res_normalize,
+                      const float* ca, const int32_t* seg_ca, const float* cb, const int32_t* seg_cb,
+                      const float* den_in, float* den_out,
+                      int32_t* out_local, int32_t* out_global, int32_t screen_terms,
+                      void* workspace, int64_t workspace_bytes, void* stream, const uint16_t* pair_table);
+int32_t rqsid_assign_plan_pair(int32_t x_format, int64_t n_rows, int32_t dim, int32_t n_segments,
+                               int32_t cand_count_max, int32_t res_levels, int32_t res_normalize,
+                               int32_t screen_terms, int32_t has_cand_lid, int32_t has_den_out, int32_t has_pair);
 
 /* The k nearest allowed centres of every row, exactly: rqsid_assign's question asked for the first k places.
  * Segments, tiles (rqsid_bucket with rqsid_assign_tile_rows()), candidate lists, x_format and the fused residual

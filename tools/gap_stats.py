@@ -26,7 +26,22 @@ def level_gaps(v, c, allowed=None):
 
 
 ACC = (16 + (512 // 16) / 2 + 1) * 2.0 ** -23 * 1.02  # assign.hip accumulation_rel
-MODES = {"1term": (1, 1, 1), "xsplit": (0, 1, 1), "3term": (0, 0, 1), "3term_acc/4": (0, 0, 0.25)}
+# "fp8corr": the 1-term bound's rounding parts cut by 2^-4 (correction products in fp8);
+# "2term_pair": terms vh.(ch + cl), the row-rounding part charged pairwise against the row's best
+# candidate (pair_ambiguous below)
+MODES = {"1term": (1, 1, 1), "xsplit": (0, 1, 1), "3term": (0, 0, 1), "3term_acc/4": (0, 0, 0.25),
+         "fp8corr": (2.0 ** -4, 2.0 ** -4, 1), "2term_global": (1, 0, 1), "2term_pair": (0, 0, 1)}
+
+
+def pair_ambiguous(sc, cd, xr, eg, allowed=None):
+    """2-term screen with the pairwise row-rounding bound: b = the row's least approximate score; candidate
+    k stays iff sc_k - sc_b <= xr |c_k - c_b| + eg_k + eg_b (xr = 2/den |ex|, eg = the global remainder).
+    Returns the per-row pass counts."""
+    scm = sc if allowed is None else torch.where(allowed, sc, torch.full_like(sc, float("inf")))
+    sb, b = scm.min(1)
+    T = torch.cdist(cd, cd, compute_mode="donot_use_mm_for_euclid_dist")
+    thr = xr[:, None] * T[b] + eg + eg.gather(1, b[:, None])
+    return ((scm - sb[:, None]) <= thr).sum(1)
 
 
 def emulated_ambiguous(v_pre, c, allowed=None):
@@ -46,6 +61,8 @@ def emulated_ambiguous(v_pre, c, allowed=None):
     for name, (fx, fc, fa) in MODES.items():
         if name == "1term":
             dot = vh @ ch.T
+        elif name.startswith("2term"):
+            dot = vh @ cd.T
         elif name == "xsplit":
             dot = vd @ ch.T
         else:
@@ -54,6 +71,11 @@ def emulated_ambiguous(v_pre, c, allowed=None):
         A = 2.0 / den * (fx * ex + fa * ACC * hn)
         B = 2.0 / den * hn * fc
         e = A[:, None] * cd.norm(dim=1)[None, :] + B[:, None] * ec[None, :]
+        if name == "2term_pair":
+            npass = pair_ambiguous(sc, cd, 2.0 / den * ex, e, allowed)
+            out[name] = out[name + "_loose"] = (npass > 1).double().sum().item()
+            out[name + "_loose_ovf8"] = (npass > 8).double().sum().item()
+            continue
         ub, lb = sc + e, sc - e
         if allowed is not None:
             ub = torch.where(allowed, ub, torch.full_like(ub, float("inf")))
