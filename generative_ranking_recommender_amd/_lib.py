@@ -22,9 +22,9 @@ SRCS = [PKG / "csrc" / "rqsid.hip", PKG / "csrc" / "assign.hip", PKG / "csrc" / 
         PKG / "csrc" / "assign_resident.hip", PKG / "csrc" / "assign_rows.hip", PKG / "csrc" / "assign_pc.hip",
         PKG / "csrc" / "auction.hip",
         PKG / "csrc" / "auction_seg.hip", PKG / "csrc" / "quant_error.hip", PKG / "csrc" / "assign_topk.hip",
-        PKG / "csrc" / "beam.hip", PKG / "csrc" / "silhouette.hip"]
+        PKG / "csrc" / "beam.hip", PKG / "csrc" / "silhouette.hip", PKG / "csrc" / "row_knn.hip"]
 DEPS = SRCS + [PKG / "csrc" / "internal.h", PKG / "csrc" / "assign_common.h", PKG / "csrc" / "assign_plan.h",
-               PKG / "csrc" / "topk_kernel.h", PKG / "csrc" / "exact_row.h"]
+               PKG / "csrc" / "topk_kernel.h", PKG / "csrc" / "exact_row.h", PKG / "csrc" / "tile_rows.h"]
 HEADER = REPO / "include" / "rqsid.h"
 # host-only I/O library (CSV reader): plain g++, no GPU code
 IO_LIB_PATH = PKG / "librqsid_io.so"
@@ -88,6 +88,10 @@ SIGNATURES = {
     "rqsid_silhouette_workspace_bytes": (c_i64, [c_i64, c_i32, c_i32]),
     "rqsid_silhouette": (c_i32, [c_vp, c_i32, c_i64, c_i32, c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_i32,
                                  c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "rqsid_row_knn_tile_rows": (c_i32, []),
+    "rqsid_row_knn_workspace_bytes": (c_i64, [c_i64, c_i32, c_i32, c_i32]),
+    "rqsid_row_knn": (c_i32, [c_vp, c_i32, c_i64, c_i32, c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp,
+                              c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "rqsid_scale_groups": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp]),
     "rqsid_centroid_tile_rows": (c_i32, []),
     "rqsid_centroid_accumulate": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_i64, c_vp, c_vp]),

@@ -987,6 +987,23 @@ class HierarchicalRQKMeans:
         x, _ = shard_rows(X, self.device, None)
         return cluster_report(self._encoder(False), x, sample=sample, seed=seed, against=against)
 
+    def neighbor_quality(self, X: np.ndarray, sample: int = 50000, seed: int = 0, k: int = 10,
+                         metric: str = "cosine") -> Dict:
+        """Neighbourhood preservation of the training-consistent IDs of ``X``: of a sampled row's ``k`` exact nearest
+        rows in the raw space, how many share its first 1 / 2 / 3 IDs (neighbor_report.py has the keys).  Single
+        process only: with a process group it raises."""
+        if not self.is_trained or not self.cluster_centers_list:
+            raise RuntimeError("Model not trained. Call train() first or load a trained model.")
+        if X.shape[1] != self.config.embedding_dim:
+            raise ValueError(f"Input dimension {X.shape[1]} does not match config embedding_dim "
+                             f"{self.config.embedding_dim}")
+        if self.group is not None:
+            raise NotImplementedError("neighbor_quality: the multi-GPU form is not built (single process only)")
+        from .neighbor_report import neighbor_report
+        from .quant_report import shard_rows
+        x, _ = shard_rows(X, self.device, None)
+        return neighbor_report(self._encoder(False), x, sample=sample, seed=seed, k=k, metric=metric)
+
     def gather_ids(self, ids_local: torch.Tensor) -> torch.Tensor:
         """All ranks' IDs in row order (one variable-size all_gather of int32 rows)."""
         if self.group is None:

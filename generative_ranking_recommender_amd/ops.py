@@ -720,6 +720,92 @@ def silhouette(x: torch.Tensor, order: Optional[torch.Tensor], seg_row_off: torc
     return a, b, b_seg, s
 
 
+KNN_MAX = 16
+KNN_METRICS = {"l2": 0, "cosine": 1}
+
+
+class RowKnnWorkspace:
+    """Scratch of rqsid_row_knn: the norm terms of rows and queries, one list of k + 8 (value, row) pairs and one
+    record per query and chunk and, in bytes [0, 4), the sticky error word (rqsid_silhouette's three bits), zeroed
+    here once; bytes [4, 16) are the call's three counters."""
+
+    def __init__(self, n_rows: int, n_queries: int, k: int, device, chunk_rows: int = 0):
+        self.bytes = int(lib().rqsid_row_knn_workspace_bytes(n_rows, n_queries, k, chunk_rows))
+        if self.bytes < 0:
+            _lib.check(self.bytes, "rqsid_row_knn_workspace_bytes")
+        self.buf = torch.empty(max(self.bytes, 256), dtype=torch.uint8, device=device)
+        self.buf[:256].zero_()
+        self.n_rows, self.n_queries, self.k, self.chunk_rows = n_rows, n_queries, k, chunk_rows
+
+    def error_word(self) -> torch.Tensor:
+        return self.buf[:4].view(torch.int32)
+
+    def counters(self) -> dict:
+        """Of the last call (one host sync): queries ranked from their lists alone, (query, chunk) pairs that took
+        the all-rows pass, queries without an answer."""
+        c = self.buf[4:16].view(torch.int32).tolist()
+        return {"from_lists": c[0], "all_rows_pairs": c[1], "non_finite_queries": c[2]}
+
+
+def row_knn_tile_rows() -> int:
+    return int(lib().rqsid_row_knn_tile_rows())
+
+
+def row_knn(x: torch.Tensor, q: torch.Tensor, k: int, metric: str = "l2", order: Optional[torch.Tensor] = None,
+            seg_row_off: Optional[torch.Tensor] = None, query_self: Optional[torch.Tensor] = None,
+            query_seg: Optional[torch.Tensor] = None, chunk_rows: int = 0,
+            workspace: Optional[RowKnnWorkspace] = None, check: Optional[bool] = None):
+    """The exact k nearest rows of ``x`` for every row of ``q`` (include/rqsid.h rqsid_row_knn).
+
+    ``x``: float32 / float16 / bfloat16 [N, D]; ``q``: [M, D] of x's dtype; ``metric``: "l2" or "cosine"; ``order``:
+    i32 [N], the rows grouped by segment (``Buckets.row_index``; None = identity); ``seg_row_off``: i32 [S + 1] or
+    None (no segments: every query searches every row); ``query_self``: i32 [M], the row of x that is the query, or
+    -1 (None = all -1); ``query_seg``: i32 [M], the segment the query searches, or -1 for every row (None = all -1).
+    Returns ``(rows, val)``: i32 [M, k], f32 [M, k] (distance or cosine similarity; -1 / +inf past the eligible
+    rows).  ``check`` (default: on unless the stream is being captured): read the workspace's error word after the
+    call (one host sync) and raise if a table entry was clamped."""
+    if check is None:
+        check = not torch.cuda.is_current_stream_capturing()
+    x_format = ROW_FORMATS.get(x.dtype)
+    if x_format is None:
+        raise ValueError(f"rqsid_row_knn reads float32, float16 or bfloat16 rows, not {x.dtype}")
+    if metric not in KNN_METRICS:
+        raise ValueError(f"rqsid_row_knn: metric must be 'l2' or 'cosine', not {metric!r}")
+    if not 1 <= int(k) <= KNN_MAX:
+        raise ValueError(f"rqsid_row_knn: k must lie in 1..{KNN_MAX}, not {k}")
+    if x.dim() != 2 or q.dim() != 2 or q.shape[1] != x.shape[1] or q.dtype != x.dtype:
+        raise ValueError("rqsid_row_knn: x [N, D] and q [M, D] must share dtype and D")
+    _require_device(x, q, order, seg_row_off, query_self, query_seg)
+    n, d = x.shape
+    m = q.shape[0]
+    if order is not None and (order.dtype != torch.int32 or order.numel() != n):
+        raise ValueError("rqsid_row_knn: order must be int32 [N]")
+    if seg_row_off is not None and (seg_row_off.dtype != torch.int32 or seg_row_off.dim() != 1
+                                    or seg_row_off.numel() < 2):
+        raise ValueError("rqsid_row_knn: seg_row_off must be int32 [S + 1]")
+    if query_seg is not None and seg_row_off is None:
+        raise ValueError("rqsid_row_knn: query_seg needs seg_row_off")
+    for name, t in (("query_self", query_self), ("query_seg", query_seg)):
+        if t is not None and (t.dtype != torch.int32 or t.numel() != m):
+            raise ValueError(f"rqsid_row_knn: {name} must be int32 [M]")
+    dev = x.device
+    rows = torch.empty((m, k), dtype=torch.int32, device=dev)
+    val = torch.empty((m, k), dtype=torch.float32, device=dev)
+    need = int(lib().rqsid_row_knn_workspace_bytes(n, m, k, chunk_rows))
+    if need < 0:
+        _lib.check(need, "rqsid_row_knn_workspace_bytes")
+    if workspace is None or workspace.bytes < need:
+        workspace = RowKnnWorkspace(n, m, k, dev, chunk_rows)
+    n_seg = 0 if seg_row_off is None else seg_row_off.numel() - 1
+    _lib.check(lib().rqsid_row_knn(_ptr(x), x_format, n, d, _ptr(order), n_seg, _ptr(seg_row_off), _ptr(q), m,
+                                   _ptr(query_self), _ptr(query_seg), KNN_METRICS[metric], int(k), chunk_rows,
+                                   _ptr(rows), _ptr(val), _ptr(workspace.buf), workspace.bytes, _stream()),
+               "rqsid_row_knn")
+    if check:
+        check_error_words([workspace.error_word()], "rqsid_row_knn", SILHOUETTE_WORD)
+    return rows, val
+
+
 def scale_groups(x: torch.Tensor, group_dims: Sequence[int], weights: Sequence[float]) -> torch.Tensor:
     _require_device(x)
     n, d = x.shape

@@ -32,8 +32,15 @@ class SemanticIDTrainer:
 
     def __init__(self, config, use_test_config: bool = False, device=None, group=None,
                  report_quantization: bool = False, report_margins: bool = False, report_beam: int = 0,
-                 report_clusters: int = 0):
+                 report_clusters: int = 0, report_neighbors: int = 0):
         self.config = config
+        # opt-in (a sample size): also write neighbor_report.json (HierarchicalRQKMeans.neighbor_quality of the
+        # training rows: how many of a row's exact nearest rows share its ID prefix, per depth).  Single process
+        # only: refused here, before any training
+        self.report_neighbors = int(report_neighbors or 0)
+        if group is not None and self.report_neighbors:
+            raise NotImplementedError("SemanticIDTrainer: report_neighbors is single-process only (the multi-GPU "
+                                      "neighbour report is not built)")
         # opt-in (a sample size, the reference's is 50000): also write cluster_quality_report.json
         # (HierarchicalRQKMeans.cluster_quality of the training rows: the three scores of the reference's
         # calculate_metrics.py per prefix depth).  Single process only: refused here, before any training
@@ -115,6 +122,10 @@ class SemanticIDTrainer:
             clusters = model.cluster_quality(vectors, sample=self.report_clusters)
             rq_io.write_json(str(self.output_dir / "cluster_quality_report.json"), clusters)
             result["cluster_quality_report"] = clusters
+        if self.report_neighbors:
+            neighbors = model.neighbor_quality(vectors, sample=self.report_neighbors)
+            rq_io.write_json(str(self.output_dir / "neighbor_report.json"), neighbors)
+            result["neighbor_report"] = neighbors
         return result
 
     def _generate_semantic_ids(self, song_ids: list, train_result: Dict) -> Dict:

@@ -379,6 +379,47 @@ int rqsid_silhouette(const void* x, int32_t x_format, int64_t n_rows, int32_t di
                      int32_t chunk_rows, float* out_a, float* out_b, int32_t* out_b_seg, float* out_s,
                      void* workspace, int64_t workspace_bytes, void* stream);
 
+/* The exact k nearest rows of every query, over all rows or inside one segment of the bucketed order (DESIGN.md
+ * 3.3c): the batched form of the reference's Evaluator.find_neighbors (src/semantic_id_generator/
+ * evaluate_semantic_ids.py) and the base of neighbourhood-preservation reports, without any distance matrix.
+ * x, x_format, row_index, n_segments, seg_row_off, q, query_self and chunk_rows mean what they mean for
+ * rqsid_silhouette (the output of rqsid_bucket serves as it is); n_segments == 0 with seg_row_off NULL is allowed:
+ * every query is then unrestricted.  Query i searches the rows at positions [seg_row_off[s], seg_row_off[s+1]) of
+ * the order when s = query_seg[i] >= 0, every row when s == -1 or query_seg is NULL; the row query_self[i] is
+ * excluded by INDEX, never by value.
+ * Key, in fp64 from the widened elements, lanes over 16-byte pieces and the re-score's halving reduction:
+ *   RQSID_KNN_L2      d2 = sum((double) q_i - (double) x_i)^2, ascending; out_val = fl32(sqrt(d2));
+ *   RQSID_KNN_COSINE  sim = dot / (sqrt(qq) sqrt(xx)), descending; out_val = fl32(sim).
+ * Ties in the key go to the lowest ROW NUMBER of x: the output is a function of the row set alone, and chunk_rows
+ * or a permutation of row_index inside segments leave every output byte unchanged.  out_row / out_val are
+ * [n_queries][k]; slots beyond the number of eligible rows hold -1 / +inf.  A base row with a non-finite element
+ * (cosine: or of zero norm) is never a neighbour; a query with a non-finite element (cosine: or of zero norm) gets
+ * -1 / NaN in every slot and is counted.
+ * Method: an fp32 screen on v_mfma_f32_32x32x2_f32 keeps the k + 8 smallest screen values per (query, chunk) with a
+ * derived interval e >= |s - t|; a (query, chunk) pair whose list cannot be proven complete (more than 8 rows inside
+ * the interval around the k-th place: true ties, duplicated rows; or a value outside the interval's premises) is
+ * walked row by row in fp64.  e, the slack and chunk_rows move only the amount of fp64 work.
+ * Limits: 1 <= k <= RQSID_KNN_MAX; dim % 32 == 0, dim <= 1024; n_rows < 2^31; x and q 16-byte aligned; chunk_rows 0
+ * (automatic) or a positive multiple of rqsid_row_knn_tile_rows(); n_queries == 0 or n_rows == 0 succeeds without
+ * touching anything.  RQSID_E_ARG / RQSID_E_WORKSPACE before any HIP call (a query_seg without seg_row_off is
+ * RQSID_E_ARG).  Stream-ordered, no host synchronisation, graph-capturable; no float atomics; no write takes its
+ * position from a device counter.
+ * Workspace (rqsid_row_knn_workspace_bytes): bytes [0, 4) the sticky error word with rqsid_silhouette's three bits
+ * (1, 2, 4; row_index is checked whole), zeroed by the caller once; bytes [4, 16) three int32 counters zeroed by every
+ * call: queries ranked from their lists alone, (query, chunk) pairs that took the all-rows pass, queries without an
+ * answer (non-finite / zero norm). */
+#define RQSID_KNN_MAX 16
+#define RQSID_KNN_L2 0
+#define RQSID_KNN_COSINE 1
+int32_t rqsid_row_knn_tile_rows(void);
+int64_t rqsid_row_knn_workspace_bytes(int64_t n_rows, int32_t n_queries, int32_t k, int32_t chunk_rows);
+int rqsid_row_knn(const void* x, int32_t x_format, int64_t n_rows, int32_t dim,
+                  const int32_t* row_index, int32_t n_segments, const int32_t* seg_row_off,
+                  const void* q, int32_t n_queries, const int32_t* query_self, const int32_t* query_seg,
+                  int32_t metric, int32_t k, int32_t chunk_rows,
+                  int32_t* out_row, float* out_val,
+                  void* workspace, int64_t workspace_bytes, void* stream);
+
 /* y = x * w_g per dimension group (hierarchical_rq_kmeans.py:583-604). */
 int rqsid_scale_groups(const float* x, int64_t n, int32_t dim, const int32_t* group_dims,
                        int32_t n_groups, const float* weights, float* out, void* stream);
