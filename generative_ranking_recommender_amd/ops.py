@@ -651,26 +651,59 @@ def quant_error(x: torch.Tensor, centers: Sequence[torch.Tensor], ids: Sequence[
     return err.t(), x_norm, sums
 
 
-class SilhouetteWorkspace:
-    """Scratch of rqsid_silhouette: squared norms of rows and queries, one record per query and chunk and, in bytes
-    [0, 4), the sticky error word (1: a row_index / query_self entry outside the rows, 2: a query_seg entry outside
-    [-1, n_segments), 4: a seg_row_off entry outside [0, n_rows] or decreasing), zeroed here once."""
+class _RowPairWorkspace:
+    """What the workspaces of rqsid_silhouette and rqsid_row_knn share: ``bytes`` from the entry's size query,
+    ``buf``, and its 256-byte header, zeroed here once, whose bytes [0, 4) are the sticky error word (1: a row_index /
+    query_self entry outside the rows, 2: a query_seg entry outside [-1, n_segments), 4: a seg_row_off entry outside
+    [0, n_rows] or decreasing)."""
 
-    def __init__(self, n_rows: int, n_queries: int, device, chunk_rows: int = 0):
-        self.bytes = int(lib().rqsid_silhouette_workspace_bytes(n_rows, n_queries, chunk_rows))
+    def __init__(self, what: str, size: int, device):
+        self.bytes = int(size)
         if self.bytes < 0:
-            _lib.check(self.bytes, "rqsid_silhouette_workspace_bytes")
+            _lib.check(self.bytes, what)
         self.buf = torch.empty(max(self.bytes, 256), dtype=torch.uint8, device=device)
         self.buf[:256].zero_()
-        self.n_rows, self.n_queries, self.chunk_rows = n_rows, n_queries, chunk_rows
 
     def error_word(self) -> torch.Tensor:
         return self.buf[:4].view(torch.int32)
 
 
+class SilhouetteWorkspace(_RowPairWorkspace):
+    """Scratch of rqsid_silhouette: squared norms of rows and queries and one record per query and chunk."""
+
+    def __init__(self, n_rows: int, n_queries: int, device, chunk_rows: int = 0):
+        super().__init__("rqsid_silhouette_workspace_bytes",
+                         lib().rqsid_silhouette_workspace_bytes(n_rows, n_queries, chunk_rows), device)
+        self.n_rows, self.n_queries, self.chunk_rows = n_rows, n_queries, chunk_rows
+
+
 SILHOUETTE_WORD = ("bit 1: a row_index or query_self entry outside [0, n_rows) was skipped; bit 2: a query_seg entry "
                    "outside [-1, n_segments) was taken as -1; bit 4: a seg_row_off entry outside [0, n_rows] or "
                    "decreasing was clamped (include/rqsid.h rqsid_silhouette)")
+
+
+def _row_pair_args(who: str, x, q, order, seg_row_off, query_self, query_seg, seg_optional: bool):
+    """The tensors rqsid_silhouette and rqsid_row_knn share, validated: ``(x_format, N, D, M)``.  ``seg_optional``:
+    ``seg_row_off`` may be None (and ``query_seg`` then has to be)."""
+    x_format = ROW_FORMATS.get(x.dtype)
+    if x_format is None:
+        raise ValueError(f"{who} reads float32, float16 or bfloat16 rows, not {x.dtype}")
+    if x.dim() != 2 or q.dim() != 2 or q.shape[1] != x.shape[1] or q.dtype != x.dtype:
+        raise ValueError(f"{who}: x [N, D] and q [M, D] must share dtype and D")
+    _require_device(x, q, order, seg_row_off, query_self, query_seg)
+    n, d = x.shape
+    m = q.shape[0]
+    if order is not None and (order.dtype != torch.int32 or order.numel() != n):
+        raise ValueError(f"{who}: order must be int32 [N]")
+    if not (seg_optional and seg_row_off is None) and (
+            seg_row_off.dtype != torch.int32 or seg_row_off.dim() != 1 or seg_row_off.numel() < 2):
+        raise ValueError(f"{who}: seg_row_off must be int32 [S + 1]")
+    if query_seg is not None and seg_row_off is None:
+        raise ValueError(f"{who}: query_seg needs seg_row_off")
+    for name, t in (("query_self", query_self), ("query_seg", query_seg)):
+        if t is not None and (t.dtype != torch.int32 or t.numel() != m):
+            raise ValueError(f"{who}: {name} must be int32 [M]")
+    return x_format, n, d, m
 
 
 def silhouette_tile_rows() -> int:
@@ -689,21 +722,7 @@ def silhouette(x: torch.Tensor, order: Optional[torch.Tensor], seg_row_off: torc
     captured): read the workspace's error word after the call (one host sync) and raise if a table entry was clamped."""
     if check is None:
         check = not torch.cuda.is_current_stream_capturing()
-    x_format = ROW_FORMATS.get(x.dtype)
-    if x_format is None:
-        raise ValueError(f"rqsid_silhouette reads float32, float16 or bfloat16 rows, not {x.dtype}")
-    if x.dim() != 2 or q.dim() != 2 or q.shape[1] != x.shape[1] or q.dtype != x.dtype:
-        raise ValueError("rqsid_silhouette: x [N, D] and q [M, D] must share dtype and D")
-    _require_device(x, order, seg_row_off, q, query_self, query_seg)
-    n, d = x.shape
-    m = q.shape[0]
-    if order is not None and (order.dtype != torch.int32 or order.numel() != n):
-        raise ValueError("rqsid_silhouette: order must be int32 [N]")
-    if seg_row_off.dtype != torch.int32 or seg_row_off.dim() != 1 or seg_row_off.numel() < 2:
-        raise ValueError("rqsid_silhouette: seg_row_off must be int32 [S + 1]")
-    for name, t in (("query_self", query_self), ("query_seg", query_seg)):
-        if t is not None and (t.dtype != torch.int32 or t.numel() != m):
-            raise ValueError(f"rqsid_silhouette: {name} must be int32 [M]")
+    x_format, n, d, m = _row_pair_args("rqsid_silhouette", x, q, order, seg_row_off, query_self, query_seg, False)
     dev = x.device
     a = torch.empty(m, dtype=torch.float32, device=dev)
     b = torch.empty(m, dtype=torch.float32, device=dev)
@@ -724,21 +743,14 @@ KNN_MAX = 16
 KNN_METRICS = {"l2": 0, "cosine": 1}
 
 
-class RowKnnWorkspace:
+class RowKnnWorkspace(_RowPairWorkspace):
     """Scratch of rqsid_row_knn: the norm terms of rows and queries, one list of k + 8 (value, row) pairs and one
-    record per query and chunk and, in bytes [0, 4), the sticky error word (rqsid_silhouette's three bits), zeroed
-    here once; bytes [4, 16) are the call's three counters."""
+    record per query and chunk; bytes [4, 16) of the header are the call's three counters."""
 
     def __init__(self, n_rows: int, n_queries: int, k: int, device, chunk_rows: int = 0):
-        self.bytes = int(lib().rqsid_row_knn_workspace_bytes(n_rows, n_queries, k, chunk_rows))
-        if self.bytes < 0:
-            _lib.check(self.bytes, "rqsid_row_knn_workspace_bytes")
-        self.buf = torch.empty(max(self.bytes, 256), dtype=torch.uint8, device=device)
-        self.buf[:256].zero_()
+        super().__init__("rqsid_row_knn_workspace_bytes",
+                         lib().rqsid_row_knn_workspace_bytes(n_rows, n_queries, k, chunk_rows), device)
         self.n_rows, self.n_queries, self.k, self.chunk_rows = n_rows, n_queries, k, chunk_rows
-
-    def error_word(self) -> torch.Tensor:
-        return self.buf[:4].view(torch.int32)
 
     def counters(self) -> dict:
         """Of the last call (one host sync): queries ranked from their lists alone, (query, chunk) pairs that took
@@ -766,28 +778,11 @@ def row_knn(x: torch.Tensor, q: torch.Tensor, k: int, metric: str = "l2", order:
     call (one host sync) and raise if a table entry was clamped."""
     if check is None:
         check = not torch.cuda.is_current_stream_capturing()
-    x_format = ROW_FORMATS.get(x.dtype)
-    if x_format is None:
-        raise ValueError(f"rqsid_row_knn reads float32, float16 or bfloat16 rows, not {x.dtype}")
     if metric not in KNN_METRICS:
         raise ValueError(f"rqsid_row_knn: metric must be 'l2' or 'cosine', not {metric!r}")
     if not 1 <= int(k) <= KNN_MAX:
         raise ValueError(f"rqsid_row_knn: k must lie in 1..{KNN_MAX}, not {k}")
-    if x.dim() != 2 or q.dim() != 2 or q.shape[1] != x.shape[1] or q.dtype != x.dtype:
-        raise ValueError("rqsid_row_knn: x [N, D] and q [M, D] must share dtype and D")
-    _require_device(x, q, order, seg_row_off, query_self, query_seg)
-    n, d = x.shape
-    m = q.shape[0]
-    if order is not None and (order.dtype != torch.int32 or order.numel() != n):
-        raise ValueError("rqsid_row_knn: order must be int32 [N]")
-    if seg_row_off is not None and (seg_row_off.dtype != torch.int32 or seg_row_off.dim() != 1
-                                    or seg_row_off.numel() < 2):
-        raise ValueError("rqsid_row_knn: seg_row_off must be int32 [S + 1]")
-    if query_seg is not None and seg_row_off is None:
-        raise ValueError("rqsid_row_knn: query_seg needs seg_row_off")
-    for name, t in (("query_self", query_self), ("query_seg", query_seg)):
-        if t is not None and (t.dtype != torch.int32 or t.numel() != m):
-            raise ValueError(f"rqsid_row_knn: {name} must be int32 [M]")
+    x_format, n, d, m = _row_pair_args("rqsid_row_knn", x, q, order, seg_row_off, query_self, query_seg, True)
     dev = x.device
     rows = torch.empty((m, k), dtype=torch.int32, device=dev)
     val = torch.empty((m, k), dtype=torch.float32, device=dev)

@@ -163,3 +163,30 @@ def fixture_t(seed=5):
     x = np.random.default_rng(seed).integers(-2, 3, (1500, 64)).astype(F32)
     x[100:140] = x[7]
     return x
+
+
+def auto_chunk_rows(n, m, target_blocks=2048):
+    """What chunk_rows = 0 stands for: the fewest chunks of whole tiles that give target_blocks blocks."""
+    tiles, qtiles = -(-n // TILE), -(-m // TILE)
+    want = max(1, min(-(-target_blocks // qtiles), tiles))
+    return -(-tiles // want) * TILE
+
+
+def block_tile_ranges(n, seg_row_off, query_seg, chunk_rows):
+    """(tile0, tile1, ntile) of every (query tile, chunk) block of the screen: a block runs the tiles of its chunk
+    that the union of its queries' position ranges touches (finite queries; -1 searches every position)."""
+    query_seg = np.asarray(query_seg)
+    chunk_rows = chunk_rows or auto_chunk_rows(n, len(query_seg))
+    lo = np.where(query_seg >= 0, seg_row_off[np.maximum(query_seg, 0)], 0).astype(np.int64)
+    hi = np.where(query_seg >= 0, seg_row_off[np.maximum(query_seg, 0) + 1], n).astype(np.int64)
+    out = []
+    for q0 in range(0, len(query_seg), TILE):
+        some = lo[q0:q0 + TILE] < hi[q0:q0 + TILE]
+        ulo = lo[q0:q0 + TILE][some].min() if some.any() else 2 ** 31 - 1
+        uhi = hi[q0:q0 + TILE][some].max() if some.any() else 0
+        for c0 in range(0, n, chunk_rows):
+            ntile = -(-(min(c0 + chunk_rows, n) - c0) // TILE)
+            tile0 = min((ulo - c0) // TILE, ntile) if ulo > c0 else 0
+            tile1 = min(-(-(uhi - c0) // TILE), ntile) if uhi > c0 else 0
+            out.append((int(tile0), int(tile1), ntile))
+    return np.array(out)

@@ -54,13 +54,14 @@ class Case:
         return self._ref[metric, restricted]
 
     def run(self, metric, k=10, chunk_rows=0, x=None, q=None, qself="own", order="own", restricted=False,
-            want_ws=False):
+            want_ws=False, qseg=None):
         x = self.x if x is None else x
         q = self.q if q is None else q
         ws = ops.RowKnnWorkspace(len(x), len(q), k, x.device, chunk_rows)
         rows, val = ops.row_knn(x, q, k, metric, order=self.order if isinstance(order, str) else order,
                                 seg_row_off=self.off, query_self=self.qself if isinstance(qself, str) else qself,
-                                query_seg=t(self.qseg_np) if restricted else None, chunk_rows=chunk_rows,
+                                query_seg=t(self.qseg_np if qseg is None else qseg) if restricted else None,
+                                chunk_rows=chunk_rows,
                                 workspace=ws, check=False)
         assert int(ws.error_word().item()) == 0
         out = (rows.cpu().numpy(), val.cpu().numpy())
@@ -209,6 +210,52 @@ def test_restricted_search(case, metric):
         assert (rows[25:30] == -1).all() and np.isposinf(val[25:30]).all()  # the empty segment
         if k > 4:  # the five-row segment, self excluded: four neighbours, then -1 / +inf
             assert (rows[:5, :4] >= 0).all() and (rows[:5, 4:] == -1).all() and np.isposinf(val[:5, 4:]).all()
+
+
+SORTED_CHUNKS = (128, 0, 1024)  # (0 is 128 at this size: one tile per chunk; 1024: eight)
+
+
+def sorted_restricted(c):
+    """The restricted queries of the case in the order of their segments: a query tile then spans a few segments,
+    and the union of its ranges leaves tiles out at both ends."""
+    keep = np.flatnonzero(c.qseg_np >= 0)
+    return keep[np.argsort(c.qseg_np[keep], kind="stable")]
+
+
+def test_sorted_queries_make_the_tile_skip_work(case_a):
+    """On the CPU (tests/_knn_model.py): blocks that start past their chunk's first tile, blocks that stop before its
+    last, both with tiles left to run, and at one tile per chunk blocks whose chunk lies outside the range."""
+    c = case_a
+    pick = sorted_restricted(c)
+    assert len(pick) == N_QUERIES - 20 and (np.diff(c.qseg_np[pick]) >= 0).all()
+    tile0, tile1, ntile = M.block_tile_ranges(len(c.x_np), c.off_np, c.qseg_np[pick], 1024).T
+    assert (ntile > 1).any()
+    assert ((tile0 > 0) & (tile0 < tile1)).any() and ((tile1 < ntile) & (tile0 < tile1)).any()
+    for chunk in (128, 0):
+        tile0, tile1, ntile = M.block_tile_ranges(len(c.x_np), c.off_np, c.qseg_np[pick], chunk).T
+        assert (ntile == 1).all()
+        assert (tile0 == 1).any() and (tile1 == 0).any() and (tile0 < tile1).any()  # wholly outside, either side
+    # the random order of the other tests skips next to nothing: that is why this input exists
+    tile0, tile1, ntile = M.block_tile_ranges(len(c.x_np), c.off_np, c.qseg_np, 128).T
+    assert (tile0 < tile1).mean() > 0.9
+
+
+@pytest.mark.parametrize("metric", METRICS)
+def test_restricted_search_sorted_queries(case_a, metric):
+    """test_restricted_search's assertions against the same brute force, on the input above."""
+    c = case_a
+    pick = sorted_restricted(c)
+    want_r, want_v = (a[pick] for a in c.ref(metric, restricted=True))
+    qseg = c.qseg_np[pick]
+    for k, chunk in zip((10, 16, 10), SORTED_CHUNKS):
+        rows, val = c.run(metric, k, chunk, q=c.q[t(pick)].contiguous(), qself=c.qself[t(pick)].contiguous(),
+                          restricted=True, qseg=qseg)
+        assert (rows == want_r[:, :k]).all() and within_one_ulp(val, want_v[:, :k]), chunk
+        assert ((rows < 0) | (c.lab[np.maximum(rows, 0)] == qseg[:, None])).all()
+        empty, five = qseg == c.n_seg - 2, qseg == c.n_seg - 1
+        assert empty.sum() == 5 and five.sum() == 5
+        assert (rows[empty] == -1).all() and np.isposinf(val[empty]).all()
+        assert (rows[five, :4] >= 0).all() and (rows[five, 4:] == -1).all() and np.isposinf(val[five, 4:]).all()
 
 
 @pytest.mark.parametrize("metric", METRICS)
