@@ -18,11 +18,23 @@
 // histograms.  A round of a wide segment is two sweeps of W when each worker's threshold stays in last
 // round's high-byte bin (guessed pass with its per-chunk tie counts, then the bids); a worker whose
 // threshold left the bin takes the exact two-pass selection and a tie-count sweep in the same round.
+//
+// Sections of this file:
+//   state and plan       SegAuction; constants tied to auction_plan.h, which decides the form of a call's rounds
+//   setup                segment / job init, min-max and eps, the N_s < K fallback
+//   sweep rounds         sa_guess_hist (+ list_append), sa_select_guess, sa_hist / sa_select / sa_eqcount / sa_eqscan
+//                        for missed workers, sa_small_select (one-chunk segments), sa_bid, sa_resolve, sa_round_end
+//   list building blocks the per-entry rules every list form shares: key refresh, the two histograms, the
+//                        selections around wave_select, the tie rank (wave_rank_bin), the bid, the failure write
+//   list rounds          one block per (segment, worker): sa_list_round; multi-block, one wide segment: sa_mlist_*
+//   host                 read_auction_env, carve (base + AuctionWorkspaceMap offset), seg_auction_run
+//   row-sharded auction  da_list_* (the lists of one rank's share) and the rqsid_dauction_* pass entries
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 
+#include "auction_plan.h"
 #include "internal.h"
 
 // diagnostic build only (-DRQSID_STAMPS, tools/auction_stamps.py): s_memtime cycles of the list round's phases
@@ -1356,16 +1368,156 @@ constexpr int kLT = 1024;  // threads of a list-round block
 // Lists of at most kLE * LT entries stay in registers from the first load (entry tid + q * LT in er[q]): the
 // later passes read no list memory, and the first load is issued before the block's validity checks.
 constexpr int kLE = 4;
+static_assert(kCh == kPlanCh && kKG == kPlanKG && kAbovePad == kPlanAbovePad && kRd == kPlanRd && kMCH == kPlanMCH &&
+                  kListEq == kPlanListEq && kLE == kPlanLE && kLT == kPlanLT && kListMaxJpw == kPlanListMaxJpw &&
+                  kListBlockJpw == kPlanListBlockJpw && kListStart == kPlanListStart &&
+                  kListStartWide == kPlanListStartWide && kListWideK == kPlanListWideK && kListDelta == kPlanListDelta,
+              "auction_plan.h plans and lays out the workspace with these constants");
+
+// ---- list building blocks: the rules of one list entry {job, raw score | key << 16} and of one worker's selection,
+// shared by the one-block (sa_list_round), multi-block (sa_mlist_*) and row-sharded (da_list_*) list rounds ----
+// this round's value key of an entry (raw score, the job's cost and last winner) and the entry's new .y, which
+// keeps the key in its upper 16 bits for the later passes; own: worker w won the job last round
+struct ListKey {
+  uint32_t k, y;
+  bool own;
+};
+__device__ __forceinline__ ListKey list_refresh_key(const SegAuction& a, int w, const uint2& e) {
+  const int32_t hbj = js_hb(a, e.x);
+  const uint32_t k = okey(value_bits(w, (uint16_t)e.y, hbj, js_cost(a, e.x)));
+  return {k, (e.y & 0xFFFFu) | (k << 16), hbj == w};
+}
+// the counting rules of the two-byte radix select over the keys >= the list base kb: high bytes, then the low
+// bytes inside the selected bin b1
+__device__ __forceinline__ void list_hist_hi(uint32_t* hst, uint32_t k, uint32_t kb) {
+  if (k >= kb) atomicAdd(&hst[k >> 8], 1u);
+}
+__device__ __forceinline__ void list_hist_lo(uint32_t* hst, uint32_t k, uint32_t kb, uint32_t b1) {
+  if (k >= kb && (k >> 8) == b1) atomicAdd(&hst[k & 255u], 1u);
+}
+// the selections from those histograms (one wave; h in LDS or global memory).  High byte: ok unless fewer than
+// jpw + 1 values lie at or above the list base (the list fails); low byte: the threshold T and need, the number of
+// values equal to T that bid
+struct ListSelHi {
+  bool ok;
+  uint32_t b1, above;
+};
+struct ListSel {
+  uint32_t T, need;
+};
+__device__ __forceinline__ ListSelHi list_select_hi(const uint32_t* h, uint32_t jpw, int lane) {
+  uint32_t tot = h[4 * lane] + h[4 * lane + 1] + h[4 * lane + 2] + h[4 * lane + 3];
+  for (int o = 32; o > 0; o >>= 1) tot += (uint32_t)__shfl_xor((int)tot, o);
+  ListSelHi s = {tot >= jpw + 1, 0, 0};
+  if (s.ok) wave_select(h, jpw + 1, s.b1, s.above);
+  return s;
+}
+__device__ __forceinline__ ListSel list_select_lo(const uint32_t* h, uint32_t jpw, uint32_t b1, uint32_t above_hi) {
+  uint32_t b = 0, above = 0;
+  wave_select(h, jpw + 1 - above_hi, b, above);
+  return {(b1 << 8) | b, jpw - (above_hi + above)};
+}
+// One byte of the radix select of the rank-th smallest tied job: the ascending walk over a 256-bin histogram by
+// one wave (tid < 64, 4 bins a lane); sh[0] = the bin holding it, sh[1] = its rank inside that bin
+__device__ __forceinline__ void wave_rank_bin(const uint32_t* hst, uint32_t rank, int tid, uint32_t* sh) {
+  const uint32_t h0 = hst[4 * tid], h1 = hst[4 * tid + 1], h2 = hst[4 * tid + 2], h3 = hst[4 * tid + 3];
+  const uint32_t own = h0 + h1 + h2 + h3;
+  uint32_t inc = own;  // inclusive prefix over lanes <= tid
+  for (int o = 1; o < 64; o <<= 1) {
+    const uint32_t y = (uint32_t)__shfl_up((int)inc, o);
+    if (tid >= o) inc += y;
+  }
+  const unsigned long long m = __ballot(inc >= rank);
+  const int Ln = m ? __ffsll((long long)m) - 1 : 63;
+  if (tid == Ln) {
+    uint32_t acc = inc - own;  // strictly below this lane's bins
+    const uint32_t hv[4] = {h0, h1, h2, h3};
+    int q = 0;
+    for (; q < 3; ++q) {
+      if (acc + hv[q] >= rank) break;
+      acc += hv[q];
+    }
+    sh[0] = (uint32_t)(4 * Ln + q);
+    sh[1] = rank - acc;
+  }
+}
+// The 16-bit bid of an entry with key k against the threshold T (value vT): a value above T bids (x - T) + eps; a
+// value equal to T bids eps when the caller's tie rule tie_bids() says it is among the first `need` in job order
+// (asked only for such values); retained: the retention rounds' override, the previous winner bids eps on its job.
+// 0: no bid.  The caller issues the packed {bid, ~worker} atomicMax of the sweep's bid kernel (list_bid_max).
+template <class Tie>
+__device__ __forceinline__ uint32_t list_bid(uint32_t k, uint32_t T, _Float16 vT, uint16_t eps, _Float16 epsh,
+                                             Tie&& tie_bids, bool retained) {
+  uint32_t bid = 0;
+  if (k > T) {
+    const _Float16 x = __builtin_bit_cast(_Float16, okey_inv(k));
+    bid = __builtin_bit_cast(uint16_t, (_Float16)((_Float16)(x - vT) + epsh));
+  } else if (k == T && tie_bids()) {
+    bid = eps;
+  }
+  return retained ? eps : bid;
+}
+__device__ __forceinline__ void list_bid_max(const SegAuction& a, uint32_t j, int w, uint32_t bid) {
+  if (bid) atomicMax(&a.key[j], (bid << 16) | (0xFFFFu - (uint32_t)w));
+}
+// a worker's list failed this round: it takes the sweep path (lbad), whose guessed pass rebuilds the list (lcnt = 0);
+// the sweep kernels run (lany) and a list-only block is replayed (live_count[3])
+__device__ __forceinline__ void list_fail(const SegAuction& a, int64_t hw) {
+  a.lbad[hw] = 1;
+  *a.lany = 1;
+  a.live_count[3] = 1;
+  a.lcnt[hw * kAbovePad] = 0;
+}
+// One pass of a worker's list L over the entry ranges `ranges` hands out (256 threads), for the forms that keep the
+// list in memory.  STEP 0: this round's keys, stored into the entries, and the high-byte histogram of the keys >= kb,
+// added to hist; 1: the low-byte histogram of bin b1; 3: the bids against T (eps of segment sg, tie(job) as
+// list_bid's rule).  STEP 2, the values equal to T, differs by form and stays with its kernel.
+template <int STEP, class Ranges, class Tie>
+__device__ __forceinline__ void list_pass(const SegAuction& a, int sg, int w, uint2* L, uint32_t kb, uint32_t b1,
+                                          uint32_t T, uint32_t* hist, Ranges&& ranges, Tie&& tie) {
+  const int tid = threadIdx.x;
+  if constexpr (STEP <= 1) {
+    __shared__ uint32_t hst[256];
+    hst[tid] = 0;
+    __syncthreads();
+    ranges([&](uint32_t i0, uint32_t i1) {
+      for (uint32_t i = i0 + tid; i < i1; i += 256) {
+        if (STEP == 0) {
+          const ListKey lk = list_refresh_key(a, w, L[i]);
+          L[i].y = lk.y;
+          list_hist_hi(hst, lk.k, kb);
+        } else {
+          list_hist_lo(hst, L[i].y >> 16, kb, b1);
+        }
+      }
+    });
+    __syncthreads();
+    if (hst[tid]) atomicAdd(&hist[tid], hst[tid]);
+  } else {
+    const uint16_t eps = a.eps[sg];
+    const _Float16 epsh = __builtin_bit_cast(_Float16, eps);
+    const _Float16 vT = __builtin_bit_cast(_Float16, okey_inv(T));
+    const bool ret = *a.round_dev < 100;
+    ranges([&](uint32_t i0, uint32_t i1) {
+      for (uint32_t i = i0 + tid; i < i1; i += 256) {
+        const uint2 e = L[i];
+        const uint32_t j = e.x;
+        list_bid_max(a, j, w, list_bid(e.y >> 16, T, vT, eps, epsh, [&] { return tie(j); }, ret && js_hb(a, j) == w));
+      }
+    });
+  }
+}
+
 template <int LT>
 __global__ __launch_bounds__(LT) void sa_list_round_kernel(SegAuction a) {
   const int64_t hw = blockIdx.x;
   const int r = (int)(hw / a.K), w = (int)(hw % a.K);
   const bool one = a.one_n > 0;  // (then n_multi == 1: r == 0, segment 0)
   const int sg = one ? 0 : a.mseg[r];
-  const uint32_t cap = one ? (uint32_t)(4 * (a.one_n / a.K) + 256) : (uint32_t)a.lcs[r];
+  const uint32_t cap = one ? (uint32_t)list_capacity(a.one_n, a.K) : (uint32_t)a.lcs[r];
   uint2* const L = a.lst + (one ? 0 : a.loff[r]) + (int64_t)w * cap;
   const int tid = threadIdx.x;
-  const bool regs = cap <= (uint32_t)(kLE * LT);
+  const bool regs = list_in_registers(cap, LT);
   // the block's state words and (register lists) the entries, all issued before any test: one round trip
   const int64_t sw = (int64_t)sg * a.K + w;
   const uint8_t sflag = a.flag[sg];
@@ -1401,12 +1553,7 @@ __global__ __launch_bounds__(LT) void sa_list_round_kernel(SegAuction a) {
     }
   };
   auto fail_list = [&]() {
-    if (tid == 0) {
-      a.lbad[hw] = 1;
-      *a.lany = 1;
-      a.live_count[3] = 1;
-      a.lcnt[hw * kAbovePad] = 0;  // the sweep's guessed pass rebuilds it
-    }
+    if (tid == 0) list_fail(a, hw);
   };
   if (n == 0 || n > cap || counter > 1000 || tprev < kb) {
     if (tid == 0) list_stat(a, list_fail_why(n, cap, counter));
@@ -1418,22 +1565,18 @@ __global__ __launch_bounds__(LT) void sa_list_round_kernel(SegAuction a) {
   // pass 1: this round's value keys (raw score, cost, last winner), kept in the entries' upper 16 bits so
   // the later passes read the list only
   visit([&](uint2& e, uint32_t i) {
-    const int32_t hbj = js_hb(a, e.x);
-    const uint32_t k = okey(value_bits(w, (uint16_t)e.y, hbj, js_cost(a, e.x)));
-    e.y = (e.y & 0xFFFFu) | (k << 16);
+    const ListKey lk = list_refresh_key(a, w, e);
+    e.y = lk.y;
     if (!regs) L[i].y = e.y;
-    else if (hbj == w) e.x |= 0x80000000u;  // (register copy only: the retention test of the bid pass)
-    if (k >= kb) atomicAdd(&hst[k >> 8], 1u);
+    else if (lk.own) e.x |= 0x80000000u;  // (register copy only: the retention test of the bid pass)
+    list_hist_hi(hst, lk.k, kb);
   });
   __syncthreads();
   if (tid < 64) {
-    uint32_t tot = hst[4 * tid] + hst[4 * tid + 1] + hst[4 * tid + 2] + hst[4 * tid + 3];
-    for (int o = 32; o > 0; o >>= 1) tot += (uint32_t)__shfl_xor((int)tot, o);
-    uint32_t b = 0, above = 0;
-    if (tot >= jpw + 1) wave_select(hst, jpw + 1, b, above);
+    const ListSelHi hi = list_select_hi(hst, jpw, tid);
     if (tid == 0) {
-      sh[0] = tot >= jpw + 1 ? b : 0xFFFFFFFFu;
-      sh[1] = above;
+      sh[0] = hi.ok ? hi.b1 : 0xFFFFFFFFu;
+      sh[1] = hi.above;
     }
   }
   __syncthreads();
@@ -1446,19 +1589,14 @@ __global__ __launch_bounds__(LT) void sa_list_round_kernel(SegAuction a) {
   __syncthreads();
   if (tid < 256) hst[tid] = 0;
   __syncthreads();
-  visit([&](uint2& e, uint32_t) {
-    const uint32_t k = e.y >> 16;
-    if (k >= kb && (k >> 8) == b1) atomicAdd(&hst[k & 255u], 1u);
-  });
+  visit([&](uint2& e, uint32_t) { list_hist_lo(hst, e.y >> 16, kb, b1); });
   __syncthreads();
   if (tid < 64) {
-    uint32_t b = 0, above = 0;
-    wave_select(hst, jpw + 1 - sh[1], b, above);
+    const ListSel s = list_select_lo(hst, jpw, b1, sh[1]);
     if (tid == 0) {
-      const uint32_t T = (b1 << 8) | b;
-      sh[2] = T;
-      sh[3] = jpw - (sh[1] + above);  // need: equal values that bid
-      sh[0] = 0;                      // equal values found (next pass)
+      sh[2] = s.T;
+      sh[3] = s.need;
+      sh[0] = 0;
     }
   }
   __syncthreads();
@@ -1481,28 +1619,7 @@ __global__ __launch_bounds__(LT) void sa_list_round_kernel(SegAuction a) {
           atomicAdd(&hst[(j >> shift) & 255u], 1u);
       });
       __syncthreads();
-      if (tid < 64) {  // ascending walk: the bin holding the rank-th smallest
-        const uint32_t h0 = hst[4 * tid], h1 = hst[4 * tid + 1], h2 = hst[4 * tid + 2], h3 = hst[4 * tid + 3];
-        const uint32_t own = h0 + h1 + h2 + h3;
-        uint32_t inc = own;  // inclusive prefix over lanes <= tid
-        for (int o = 1; o < 64; o <<= 1) {
-          const uint32_t y = (uint32_t)__shfl_up((int)inc, o);
-          if (tid >= o) inc += y;
-        }
-        const unsigned long long m = __ballot(inc >= rank);
-        const int Ln = m ? __ffsll((long long)m) - 1 : 63;
-        if (tid == Ln) {
-          uint32_t acc = inc - own;  // strictly below this lane's bins
-          const uint32_t hv[4] = {h0, h1, h2, h3};
-          int q = 0;
-          for (; q < 3; ++q) {
-            if (acc + hv[q] >= rank) break;
-            acc += hv[q];
-          }
-          sh[0] = (uint32_t)(4 * Ln + q);
-          sh[1] = rank - acc;
-        }
-      }
+      if (tid < 64) wave_rank_bin(hst, rank, tid, sh);
       __syncthreads();
       J = (J << 8) | sh[0];
       rank = sh[1];
@@ -1514,16 +1631,9 @@ __global__ __launch_bounds__(LT) void sa_list_round_kernel(SegAuction a) {
   const _Float16 vT = __builtin_bit_cast(_Float16, okey_inv(T));
   const bool ret = counter < 100;
   visit([&](uint2& e, uint32_t) {
-    const uint32_t j = e.x & 0x7FFFFFFFu, k = e.y >> 16;
-    uint32_t bid = 0;
-    if (k > T) {
-      const _Float16 x = __builtin_bit_cast(_Float16, okey_inv(k));
-      bid = __builtin_bit_cast(uint16_t, (_Float16)((_Float16)(x - vT) + epsh));
-    } else if (k == T && need && j <= J) {
-      bid = eps;
-    }
-    if (ret && (regs ? (e.x >> 31) != 0u : js_hb(a, j) == w)) bid = eps;  // retention: the previous winner bids eps
-    if (bid) atomicMax(&a.key[j], (bid << 16) | (0xFFFFu - (uint32_t)w));
+    const uint32_t j = e.x & 0x7FFFFFFFu;
+    const bool retained = ret && (regs ? (e.x >> 31) != 0u : js_hb(a, j) == w);
+    list_bid_max(a, j, w, list_bid(e.y >> 16, T, vT, eps, epsh, [&] { return need && j <= J; }, retained));
   });
   AST(__syncthreads();)
   if (tid == 0) {
@@ -1553,10 +1663,7 @@ __global__ __launch_bounds__(LT) void sa_list_round_kernel(SegAuction a) {
 // fails in any step (lok = 0, lbad = 1) takes the sweep path of the same round before any of its bids.
 __device__ __forceinline__ void mlist_fail(const SegAuction& a, int64_t hw) {
   a.lok[hw] = 0;
-  a.lbad[hw] = 1;
-  *a.lany = 1;
-  a.live_count[3] = 1;
-  a.lcnt[hw * kAbovePad] = 0;  // the sweep's guessed pass rebuilds it
+  list_fail(a, hw);
 }
 
 // validity (as sa_list_round_kernel's first test) and zeroed histograms; one block per worker
@@ -1600,25 +1707,10 @@ __global__ __launch_bounds__(256) void sa_mlist_pass_kernel(SegAuction a) {
   const int tid = threadIdx.x;
   uint2* const L = a.lst + a.loff[r] + (int64_t)w * a.lcs[r];
   const uint32_t kb = a.lkb[hw];
-  if (STEP == 0 || STEP == 1) {
-    __shared__ uint32_t hst[256];
-    hst[tid] = 0;
-    __syncthreads();
+  auto ranges = [&](auto&& f) { f(i0, i1); };  // this block's chunk of the list
+  if constexpr (STEP <= 1) {
     const uint32_t b1 = STEP == 1 ? a.lsel[hw * 4] : 0u;
-    for (uint32_t i = i0 + tid; i < i1; i += 256) {
-      if (STEP == 0) {
-        const uint2 e = L[i];
-        const uint32_t k = okey(value_bits(w, (uint16_t)e.y, js_hb(a, e.x), js_cost(a, e.x)));
-        L[i].y = (e.y & 0xFFFFu) | (k << 16);
-        if (k >= kb) atomicAdd(&hst[k >> 8], 1u);
-      } else {
-        const uint32_t k = L[i].y >> 16;
-        if (k >= kb && (k >> 8) == b1) atomicAdd(&hst[k & 255u], 1u);
-      }
-    }
-    __syncthreads();
-    if (hst[tid]) atomicAdd(&a.lh[hw * 512 + STEP * 256 + tid], hst[tid]);
-    return;
+    return list_pass<STEP>(a, 0, w, L, kb, b1, 0u, a.lh + hw * 512 + STEP * 256, ranges, [](uint32_t) { return false; });
   }
   const uint32_t T = a.lsel[hw * 4 + 2], need = a.lsel[hw * 4 + 3];
   if (STEP == 2) {
@@ -1632,32 +1724,18 @@ __global__ __launch_bounds__(256) void sa_mlist_pass_kernel(SegAuction a) {
     }
     return;
   }
-  // STEP 3: bids, exactly as sa_list_round_kernel's last pass (leq sorted by sa_mlist_eq_kernel)
-  const int sg = a.mseg[r];
+  // STEP 3: a tied job bids when its rank among the equal values' jobs (leq, sorted by sa_mlist_eq_kernel) < need
   const uint32_t neq = min(a.leqn[hw], (uint32_t)kListEq);
   const uint32_t* eqj = a.leq + hw * kListEq;
-  const uint16_t eps = a.eps[sg];
-  const _Float16 epsh = __builtin_bit_cast(_Float16, eps);
-  const _Float16 vT = __builtin_bit_cast(_Float16, okey_inv(T));
-  const bool ret = *a.round_dev < 100;
-  for (uint32_t i = i0 + tid; i < i1; i += 256) {
-    const uint2 e = L[i];
-    const uint32_t j = e.x, k = e.y >> 16;
-    uint32_t bid = 0;
-    if (k > T) {
-      const _Float16 x = __builtin_bit_cast(_Float16, okey_inv(k));
-      bid = __builtin_bit_cast(uint16_t, (_Float16)((_Float16)(x - vT) + epsh));
-    } else if (k == T && need) {
-      uint32_t lo = 0, hi = neq;  // rank of j among the equal values' jobs
-      while (lo < hi) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (eqj[mid] < j) lo = mid + 1; else hi = mid;
-      }
-      if (lo < need) bid = eps;
+  list_pass<3>(a, a.mseg[r], w, L, kb, 0u, T, nullptr, ranges, [&](uint32_t j) {
+    if (!need) return false;
+    uint32_t lo = 0, hi = neq;
+    while (lo < hi) {
+      const uint32_t mid = (lo + hi) >> 1;
+      if (eqj[mid] < j) lo = mid + 1; else hi = mid;
     }
-    if (ret && js_hb(a, j) == w) bid = eps;  // retention: the previous winner bids eps on its job
-    if (bid) atomicMax(&a.key[j], (bid << 16) | (0xFFFFu - (uint32_t)w));
-  }
+    return lo < need;
+  });
 }
 
 // the selections: STEP 0 the high byte b1 (>= jpw + 1 values at or above lkb, else the list fails); STEP 1
@@ -1673,29 +1751,22 @@ __global__ __launch_bounds__(64) void sa_mlist_select_kernel(SegAuction a) {
   const uint32_t* h = a.lh + hw * 512 + STEP * 256;
   uint32_t* sel = a.lsel + hw * 4;
   if (STEP == 0) {
-    uint32_t tot = h[4 * lane] + h[4 * lane + 1] + h[4 * lane + 2] + h[4 * lane + 3];
-    for (int o = 32; o > 0; o >>= 1) tot += (uint32_t)__shfl_xor((int)tot, o);
-    if (tot < jpw + 1) {  // fewer than jpw + 1 values at or above the list base
-      if (lane == 0) {
+    const ListSelHi hi = list_select_hi(h, jpw, lane);
+    if (lane == 0) {
+      if (!hi.ok) {  // fewer than jpw + 1 values at or above the list base
         list_stat(a, 5);
         mlist_fail(a, hw);
+      } else {
+        sel[0] = hi.b1;
+        sel[1] = hi.above;
       }
-      return;
-    }
-    uint32_t b = 0, above = 0;
-    wave_select(h, jpw + 1, b, above);
-    if (lane == 0) {
-      sel[0] = b;
-      sel[1] = above;
     }
   } else {
-    uint32_t b = 0, above = 0;
-    wave_select(h, jpw + 1 - sel[1], b, above);
+    const ListSel s = list_select_lo(h, jpw, sel[0], sel[1]);
     if (lane == 0) {
-      const uint32_t T = (sel[0] << 8) | b;
-      sel[2] = T;
-      sel[3] = jpw - (sel[1] + above);
-      if (T < a.lkb[hw]) mlist_fail(a, hw);  // (cannot happen with >= jpw + 1 values >= lkb; a guard)
+      sel[2] = s.T;
+      sel[3] = s.need;
+      if (s.T < a.lkb[hw]) mlist_fail(a, hw);  // (cannot happen with >= jpw + 1 values >= lkb; a guard)
     }
   }
 }
@@ -1756,7 +1827,7 @@ __global__ void sa_list_layout_kernel(SegAuction a) {
   int64_t off = 0;
   for (int r = 0; r < a.n_multi; ++r) {
     const int s = a.mseg[r];
-    const int64_t cap = 4 * ((int64_t)(a.seg_off[s + 1] - a.seg_off[s]) / a.K) + 256;
+    const int64_t cap = list_capacity(a.seg_off[s + 1] - a.seg_off[s], a.K);
     a.loff[r] = off;
     a.lcs[r] = (int32_t)cap;
     off += cap * a.K;
@@ -1876,96 +1947,51 @@ __global__ __launch_bounds__(1024) void sa_multi_index_kernel(SegAuction a) {
   if (threadIdx.x == 0) a.live_count[1] = carry;
 }
 
-struct Carve {
-  char* p;
-  int64_t used = 0;
-  template <class T>
-  T* take(int64_t n) {
-    T* r = reinterpret_cast<T*>(p + used);
-    used += (n * (int64_t)sizeof(T) + 255) / 256 * 256;
-    return r;
-  }
-};
-
-// workspace layout (also the size query when p == nullptr)
-void carve(SegAuction& a, Carve& c, int64_t N, int32_t K, int32_t S, int64_t total_chunks, bool guess,
-           bool dlist = false) {
-  a.flag = c.take<uint8_t>(S);
-  a.eps = c.take<uint16_t>(S);
-  a.mm = c.take<uint32_t>(2 * (int64_t)S);
-  a.have = c.take<uint32_t>(S);
-  a.live_count = c.take<uint32_t>(4);
-  a.round_dev = c.take<int32_t>(1);
-  a.hidx = c.take<int32_t>(S);
-  a.mseg = c.take<int32_t>(a.n_multi > 0 ? a.n_multi : 1);
-  a.cost = c.take<uint16_t>(N);
-  a.hb = c.take<int32_t>(N);
-  a.nobid = c.take<uint8_t>(N);
-  a.key = c.take<uint32_t>(N);
-  a.hist = c.take<uint32_t>((int64_t)a.n_multi * K * 256 + (dlist ? 64 : 0));  // (+ the list failure count)
-  a.sel = c.take<uint32_t>((int64_t)S * K * 4);
-  a.eqcnt = c.take<uint32_t>((int64_t)K * total_chunks);
-  a.eqtot = c.take<uint32_t>((int64_t)S * K);
-  a.above = guess ? c.take<uint32_t>((int64_t)a.n_multi * K * kAbovePad) : nullptr;
-  a.miss = guess ? c.take<uint8_t>((int64_t)a.n_multi * K) : nullptr;
-  a.chist = guess && a.n_multi > 0 ? c.take<uint16_t>(total_chunks * K * 256) : nullptr;
-  a.any_miss = guess ? c.take<uint32_t>(1) : nullptr;
-  const bool snap = guess && a.n_multi > 0;
-  a.s_cost = snap ? c.take<uint16_t>(N) : nullptr;
-  a.s_hb = snap ? c.take<int32_t>(N) : nullptr;
-  a.s_nobid = snap ? c.take<uint8_t>(N) : nullptr;
-  a.s_out = snap ? c.take<int32_t>(N) : nullptr;
-  a.s_sel = snap ? c.take<uint32_t>((int64_t)S * K * 4 + 1) : nullptr;  // + the round number
-  a.s_flag = snap ? c.take<uint8_t>(S) : nullptr;
-  a.s_rounds = snap ? c.take<int32_t>(S) : nullptr;
-  // the bid lists of the multi-chunk segments (RQSID_AUCTION_LIST=0: the sweep, for A/B): segment s holds
-  // K * (4 * (N_s / K) + 256) <= 4 N_s + 256 K entries
-  // Only while a worker's list is short enough for its one block: at ~80k jobs per worker (K=128 over 10M
-  // rows) the one-block-per-worker list round lost to the sweep (10M PROD training, level 1: 23 -> 33 s)
-  const char* el = getenv("RQSID_AUCTION_LIST");
-  const int64_t nm = a.n_multi > 0 ? a.n_multi : 1;
-  const int lmode = el ? atoi(el) : 1;  // 0: sweep only; 1: lists (default); 2: one-block lists at any size
-  // one wide segment with long lists: the multi-block list rounds (any jobs per worker); otherwise one block
-  // per worker while the lists are short
-  const char* emb = getenv("RQSID_LIST_MB_JPW");  // (A/B) the jobs per worker above which lists go multi-block
-  const int64_t mb_jpw = emb ? std::max<int64_t>(1, atoll(emb)) : kListBlockJpw;
-  const bool mb = guess && a.n_multi == 1 && lmode == 1 && N / K > mb_jpw;
-  const bool list = guess && a.n_multi > 0 && lmode != 0 && (lmode == 2 || mb || N / (nm * K) <= kListMaxJpw);
-  a.lmb_chunks = mb ? (int32_t)((4 * (N / K) + 256 + kMCH - 1) / kMCH) : 0;
-  a.lh = mb ? c.take<uint32_t>(nm * K * 512) : nullptr;
-  a.lsel = mb ? c.take<uint32_t>(nm * K * 4) : nullptr;
-  a.leq = mb ? c.take<uint32_t>(nm * K * kListEq) : nullptr;
-  a.leqn = mb ? c.take<uint32_t>(nm * K) : nullptr;
-  a.lok = mb ? c.take<uint8_t>(nm * K) : nullptr;
-  a.lst = list ? c.take<uint2>(4 * N + 256 * (int64_t)K * nm) : nullptr;
-  a.lcnt = list ? c.take<uint32_t>(nm * K * kAbovePad) : nullptr;
-  a.lkb = list ? c.take<uint32_t>(nm * K) : nullptr;
-  a.lbad = list ? c.take<uint8_t>(nm * K) : nullptr;
-  a.loff = list ? c.take<int64_t>(nm) : nullptr;
-  a.lcs = list ? c.take<int32_t>(nm) : nullptr;
-  a.lany = list ? c.take<uint32_t>(1) : nullptr;
-  const char* ej = getenv("RQSID_LIST_JS");  // 0: the list rounds gather winner and cost separately (A/B)
-  a.js = list && K <= 65535 && !(ej && atoi(ej) == 0) ? c.take<uint32_t>(N) : nullptr;
-  const char* ls = getenv("RQSID_LIST_START");
-  a.lstart = ls ? std::max(1, atoi(ls)) : K >= kListWideK ? kListStartWide : kListStart;
-  const char* ed = getenv("RQSID_LIST_DELTA");
-  a.ldelta = ed ? std::min(128, std::max(1, atoi(ed))) : kListDelta;
-  a.rdone = guess && S == 1 && a.n_multi == 1 ? c.take<unsigned long long>(16 * (1 + kRd)) : nullptr;
-  const char* es = getenv("RQSID_LIST_STATS");
-  a.lstat = list && es && atoi(es) ? c.take<uint32_t>(8) : nullptr;
-  if (dlist) {  // the row-sharded auction's lists: one rank's share, 8 * (N / K) + 256 entries per worker
-    a.dcap = 8 * (N / K) + 256;
-    a.dnb = (int32_t)std::max<int64_t>(1, (4 * (N / K) + 256 + kMCH - 1) / kMCH);
-    a.lst = c.take<uint2>(a.dcap * K);
-    a.lcnt = c.take<uint32_t>((int64_t)K * kAbovePad);
-    a.lkb = c.take<uint32_t>(K);
-    a.lbad = c.take<uint8_t>(K);
-    a.lany = c.take<uint32_t>(1);
-    a.lsel = c.take<uint32_t>((int64_t)K * 4);
-    const char* ed2 = getenv("RQSID_DAUCTION_LIST");
-    a.dlist_on = ed2 ? atoi(ed2) != 0 : 1;
-  }
+// every switch of this file (auction_plan.h documents them), read once per ABI call: a process may change one
+// between two calls
+AuctionEnv read_auction_env() {
+  AuctionEnv e;
+  auto num = [](const char* name, int& v) {
+    if (const char* s = getenv(name)) v = atoi(s);
+  };
+  num("RQSID_AUCTION_LIST", e.auction_list);
+  if (const char* s = getenv("RQSID_LIST_MB_JPW")) e.list_mb_jpw = atoll(s);
+  num("RQSID_LIST_JS", e.list_js);
+  num("RQSID_LIST_START", e.list_start);
+  num("RQSID_LIST_DELTA", e.list_delta);
+  num("RQSID_LIST_STATS", e.list_stats);
+  num("RQSID_DAUCTION_LIST", e.dauction_list);
+  num("RQSID_LIST_BLOCK", e.list_block);
+  num("RQSID_LIST_SMALL", e.list_small);
+  num("RQSID_LIST_ONLY", e.list_only);
+  return e;
 }
+
+AuctionShape seg_shape(int64_t n_jobs, int32_t n_workers, int32_t n_seg, int64_t total_chunks, int32_t n_multi) {
+  return {n_jobs, n_workers, n_seg, total_chunks, n_multi, true, false};
+}
+
+// the workspace's areas (base + the map's offset; null where the map has none) and the plan's list settings
+void carve(SegAuction& a, char* base, const AuctionWorkspaceMap& m, const AuctionPlan& p) {
+#define RQSID_X(name, field, bytes, count, present)                                 \
+  static_assert(sizeof(*a.field) == bytes, "auction_plan.h: element size of " #name); \
+  if (m.name >= 0) a.field = reinterpret_cast<decltype(a.field)>(base + m.name);
+  RQSID_AUCTION_AREAS(RQSID_X)
+#undef RQSID_X
+  a.lmb_chunks = p.lmb_chunks;
+  a.lstart = p.lstart;
+  a.ldelta = p.ldelta;
+  a.dcap = p.dcap;
+  a.dnb = p.dnb;
+  a.dlist_on = p.dlist_on;
+}
+
+// the 8-byte-load build of a sweep kernel (load_chunk<true>) or the 2-byte one
+void launch_vec(bool vec, void (*k8)(SegAuction), void (*k2)(SegAuction), dim3 grid, hipStream_t st,
+                const SegAuction& a) {
+  hipLaunchKernelGGL(vec ? k8 : k2, grid, dim3(256), 0, st, a);
+}
+
 
 }  // namespace
 }  // namespace rqsid
@@ -1979,11 +2005,8 @@ int32_t rqsid_seg_auction_chunk_jobs(void) { return kCh; }
 int64_t rqsid_seg_auction_workspace_bytes(int64_t n_jobs, int32_t n_workers, int32_t n_seg, int64_t total_chunks,
                                           int32_t n_multi) {
   if (n_jobs < 0 || n_workers <= 0 || n_seg <= 0 || total_chunks < 0 || n_multi < 0 || n_multi > n_seg) return -1;
-  SegAuction a{};
-  a.n_multi = n_multi;
-  Carve c{nullptr};
-  carve(a, c, n_jobs, n_workers, n_seg, total_chunks, true);
-  return c.used;
+  const AuctionShape shape = seg_shape(n_jobs, n_workers, n_seg, total_chunks, n_multi);
+  return AuctionWorkspaceMap(shape, plan_auction(shape, read_auction_env())).total_bytes;
 }
 
 int rqsid_seg_auction_lap_half(const uint16_t* scores, int32_t n_workers, int32_t n_seg, const int32_t* seg_off,
@@ -2010,8 +2033,10 @@ int seg_auction_run(const uint16_t* scores, int32_t n_workers, int32_t n_seg, co
     return fail(RQSID_E_ARG, "seg_auction: bad arguments (K=%d S=%d chunks=%lld multi=%d)", n_workers, n_seg,
                 (long long)total_chunks, n_multi);
   if (n_workers == 1) return fail(RQSID_E_ARG, "seg_auction: a single worker cannot bid on N + 1 jobs");
-  if (!workspace ||
-      workspace_bytes < rqsid_seg_auction_workspace_bytes(n_jobs, n_workers, n_seg, total_chunks, n_multi))
+  const AuctionShape shape = seg_shape(n_jobs, n_workers, n_seg, total_chunks, n_multi);
+  const AuctionPlan plan = plan_auction(shape, read_auction_env());
+  const AuctionWorkspaceMap map(shape, plan);
+  if (!workspace || workspace_bytes < map.total_bytes)
     return fail(RQSID_E_WORKSPACE, "seg_auction: workspace too small");
   hipStream_t st = (hipStream_t)stream;
   SegAuction a{};
@@ -2024,8 +2049,7 @@ int seg_auction_run(const uint16_t* scores, int32_t n_workers, int32_t n_seg, co
   a.rounds = out_rounds;
   a.n_multi = n_multi;
   a.one_n = single_layout && n_multi == 1 ? n_jobs : 0;
-  Carve c{(char*)workspace};
-  carve(a, c, n_jobs, n_workers, n_seg, total_chunks, true);
+  carve(a, (char*)workspace, map, plan);
   const unsigned gs = (unsigned)cdiv(n_seg, 256);
   // pinned readback ([0] live segments, [1] multi-chunk segments): one buffer per host thread, kept
   // for the thread's lifetime (the lockstep fits call this once per iteration)
@@ -2073,12 +2097,11 @@ int seg_auction_run(const uint16_t* scores, int32_t n_workers, int32_t n_seg, co
   // segments are no-ops, so stopping late only costs empty launches) and only a block's last round counts,
   // into a counter zeroed after each read.  The round number lives on the device, so one captured block
   // (a HIP graph of kPoll rounds) replays for every block: the auction is launch-bound at small N.
-  constexpr int kPoll = 8;
+  constexpr int kPoll = kPlanPoll;
   // list-only blocks are longer: their rounds are a few launches each, and the host's readback and launch
   // between two blocks (tens of us) cost as much as several rounds; a failed list replays the block's first
   // kPoll rounds in full from its snapshot, then the loop goes on from there
-  const char* elb = getenv("RQSID_LIST_BLOCK");  // list-only rounds per captured block (A/B; default 32)
-  const int kPollList = elb ? std::min(256, std::max(kPoll, atoi(elb))) : 32;
+  const int kPollList = plan.list_block_rounds;
   // lean rounds leave out the two-pass kernels of missed workers (five launches of a few us each, empty
   // in most rounds); a lean block runs from a snapshot of the round state and is replayed with the full
   // rounds when any worker missed in it, so the result is the full rounds' in every case
@@ -2095,15 +2118,8 @@ int seg_auction_run(const uint16_t* scores, int32_t n_workers, int32_t n_seg, co
   // resolve and round end, without the guessed pass, selection and bid sweep, whose blocks all exit when
   // every list holds but whose dispatch over total_chunks x K/16 blocks costs ~0.2 ms per kernel at K=2560
   // over 6.25M jobs.  Such a block runs from a snapshot like a lean block and is replayed in full when any
-  // list failed in it (live_count[3]).
-  const bool list_only_ok = a.lst && !any_single;
-  // short lists take 256-thread list-round blocks: capacity <= 4096 entries in every segment when there are
-  // many segments (S x K blocks per round), <= 1024 for one segment (a 100k x 128 auction, capacity 3380, ran
-  // 0.0194 -> 0.0207 ms per round with 256 threads; K=1280 x 100k, capacity 568, 0.0295 -> 0.0253)
-  const char* els = getenv("RQSID_LIST_SMALL");  // 0: always 1024 threads; n > 1: one capacity limit (A/B)
-  const int64_t lcap_max = 4 * ((int64_t)host[2] / n_workers) + 256;
-  const int64_t lsmall_cap = els && atoi(els) > 1 ? atoi(els) : (n_multi > 1 ? 4096 : 1024);
-  const bool lsmall = lcap_max <= lsmall_cap && !(els && atoi(els) == 0);
+  // list failed in it (live_count[3]).  (plan.list_only; plan.list_threads: short lists take 256-thread blocks)
+  const bool lsmall = plan.list_threads(list_capacity(host[2], n_workers)) == 256;
   auto launch_round = [&](hipStream_t q, bool count, bool lean, bool list_only = false) {
     if (a.lst && a.lmb_chunks) {
       const dim3 gw((unsigned)(n_multi * a.K)), gp((unsigned)((int64_t)n_multi * a.K * a.lmb_chunks));
@@ -2127,26 +2143,21 @@ int seg_auction_run(const uint16_t* scores, int32_t n_workers, int32_t n_seg, co
       return;
     }
     if (n_multi > 0) {
-      if (vec) hipLaunchKernelGGL((sa_guess_hist_kernel<true>), gcw, dim3(256), 0, q, a);
-      else hipLaunchKernelGGL((sa_guess_hist_kernel<false>), gcw, dim3(256), 0, q, a);
+      launch_vec(vec, sa_guess_hist_kernel<true>, sa_guess_hist_kernel<false>, gcw, q, a);
       hipLaunchKernelGGL(sa_select_guess_kernel, dim3(gmw), dim3(256), 0, q, a);
       if (!lean) {
         // the two-pass selection for the workers the guessed pass missed (every block exits at once
         // when none of its workers missed)
-        if (vec) hipLaunchKernelGGL((sa_hist_kernel<0, true>), gcw, dim3(256), 0, q, a);
-        else hipLaunchKernelGGL((sa_hist_kernel<0, false>), gcw, dim3(256), 0, q, a);
+        launch_vec(vec, sa_hist_kernel<0, true>, sa_hist_kernel<0, false>, gcw, q, a);
         hipLaunchKernelGGL((sa_select_kernel<false>), dim3(gmw), dim3(256), 0, q, a);
-        if (vec) hipLaunchKernelGGL((sa_hist_kernel<1, true>), gcw, dim3(256), 0, q, a);
-        else hipLaunchKernelGGL((sa_hist_kernel<1, false>), gcw, dim3(256), 0, q, a);
+        launch_vec(vec, sa_hist_kernel<1, true>, sa_hist_kernel<1, false>, gcw, q, a);
         hipLaunchKernelGGL((sa_select_kernel<true>), dim3(gmw), dim3(256), 0, q, a);
-        if (vec) hipLaunchKernelGGL((sa_eqcount_kernel<true>), gcw, dim3(256), 0, q, a);
-        else hipLaunchKernelGGL((sa_eqcount_kernel<false>), gcw, dim3(256), 0, q, a);
+        launch_vec(vec, sa_eqcount_kernel<true>, sa_eqcount_kernel<false>, gcw, q, a);
         hipLaunchKernelGGL(sa_eqscan_kernel, dim3(gmw), dim3(256), 0, q, a);
       }
     }
     if (any_single) hipLaunchKernelGGL(sa_small_select_kernel, gcw, dim3(256), 0, q, a);
-    if (vec) hipLaunchKernelGGL((sa_bid_kernel<true>), gcw, dim3(256), 0, q, a);
-    else hipLaunchKernelGGL((sa_bid_kernel<false>), gcw, dim3(256), 0, q, a);
+    launch_vec(vec, sa_bid_kernel<true>, sa_bid_kernel<false>, gcw, q, a);
     hipLaunchKernelGGL(sa_resolve_kernel, gc, dim3(256), 0, q, ar, out_assign);
     if (!a.rdone) hipLaunchKernelGGL(sa_round_end_kernel, dim3(gs), dim3(256), 0, q, a, (int)count);
   };
@@ -2171,25 +2182,17 @@ int seg_auction_run(const uint16_t* scores, int32_t n_workers, int32_t n_seg, co
   };
   hipGraphExec_t exec = capture(false);
   hipGraphExec_t exec_lean = n_multi > 0 && exec ? capture(true) : nullptr;
-  const char* elo = getenv("RQSID_LIST_ONLY");  // 0: no list-only blocks (A/B)
-  hipGraphExec_t exec_list = list_only_ok && exec_lean && !(elo && atoi(elo) == 0) ? capture(true, true) : nullptr;
+  hipGraphExec_t exec_list = plan.list_only && exec_lean ? capture(true, true) : nullptr;
   bool try_list = false;
   const unsigned gsnap = (unsigned)grid_cap(cdiv(std::max<int64_t>(n_jobs, (int64_t)n_seg * n_workers * 4), 256), 4096);
   if (fill_async(a.live_count, 0, 4, st) != hipSuccess) rc = fail(RQSID_E_LAUNCH, "seg_auction: memset");
   bool try_lean = false;  // round 0 misses everywhere (thresholds start at key 0)
   for (int done = 0; rc == RQSID_OK && (max_rounds <= 0 || done < max_rounds);) {
     int n = max_rounds > 0 ? std::min(kPoll, max_rounds - done) : kPoll;
-    bool lonly = try_list && exec_list && (max_rounds <= 0 || max_rounds - done >= kPollList);
-    // a list-only block must end by round 1000 (the leftover rounds > 1000 bid on unlisted pairs: every list
-    // fails there, and a failed block costs its rounds plus a full replay): the rounds up to 1000 that no
-    // whole block fits run list-only by direct launches (the list tail), from the same snapshot
-    bool ltail = false;
-    if (lonly && done + kPollList > 1001) {
-      lonly = false;
-      ltail = done < 1001 && (max_rounds <= 0 || max_rounds - done >= 1001 - done);
-      if (ltail) n = 1001 - done;
-    }
-    if (lonly) n = kPollList;
+    // list-only: a captured block, or the list tail by direct launches from the same snapshot (next_list_block)
+    const AuctionPlan::ListBlock lb = try_list && exec_list ? plan.next_list_block(done, max_rounds) : AuctionPlan::ListBlock{};
+    const bool lonly = lb.graph, ltail = lb.tail;
+    if (lonly || ltail) n = lb.rounds;
     const bool lean = !lonly && !ltail && try_lean && exec_lean && n == kPoll;
     (lonly || ltail ? n_list : lean ? n_lean : n_full) += 1;
     if (fill_async(a.live_count + 2, 0, 8, st) != hipSuccess) {
@@ -2269,8 +2272,6 @@ int seg_auction_run(const uint16_t* scores, int32_t n_workers, int32_t n_seg, co
 // count) and the segmented state with S = 1, every chunk on the global-histogram path.
 // ---------------------------------------------------------------------------------------------------------
 namespace {
-constexpr int64_t kDHeader = 512;
-
 // ---- row-sharded list rounds --------------------------------------------------------------------------------
 // The single-process list rounds (sa_list_round_kernel) with the rank's own jobs: a sweep round that starts the
 // list phase appends each worker's values of this rank's jobs with key >= lkb = T - kListDelta (T: the round's
@@ -2367,64 +2368,27 @@ __global__ __launch_bounds__(256) void da_list_pass_kernel(SegAuction a) {
   const uint32_t kb = a.lkb[w];
   const uint32_t stride = (uint32_t)a.dnb * kMCH;
   if (STEP == 0 && c0 == 0 && tid == 0 && n_raw > cap) atomicAdd(a.hist + (int64_t)a.K * 256, 1u);
-  if (STEP <= 1) {
-    __shared__ uint32_t hst[256];
-    hst[tid] = 0;
-    __syncthreads();
+  auto ranges = [&](auto&& f) {  // this block's entry chunks
+    for (uint32_t i0 = (uint32_t)c0 * kMCH; i0 < n; i0 += stride) f(i0, min(n, i0 + (uint32_t)kMCH));
+  };
+  if constexpr (STEP <= 1) {
     const uint32_t b1 = STEP == 1 ? a.sel[(int64_t)w * 4] : 0u;
-    for (uint32_t i0 = (uint32_t)c0 * kMCH; i0 < n; i0 += stride) {
-      const uint32_t i1 = min(n, i0 + (uint32_t)kMCH);
-      for (uint32_t i = i0 + tid; i < i1; i += 256) {
-        if (STEP == 0) {
-          const uint2 e = L[i];
-          const uint32_t k = okey(value_bits(w, (uint16_t)e.y, a.hb[e.x], a.cost[e.x]));
-          L[i].y = (e.y & 0xFFFFu) | (k << 16);
-          if (k >= kb) atomicAdd(&hst[k >> 8], 1u);
-        } else {
-          const uint32_t k = L[i].y >> 16;
-          if (k >= kb && (k >> 8) == b1) atomicAdd(&hst[k & 255u], 1u);
-        }
-      }
-    }
-    __syncthreads();
-    if (hst[tid]) atomicAdd(&a.hist[(int64_t)w * 256 + tid], hst[tid]);
-    return;
+    return list_pass<STEP>(a, 0, w, L, kb, b1, 0u, a.hist + (int64_t)w * 256, ranges, [](uint32_t) { return false; });
   }
   const uint32_t T = a.sel[(int64_t)w * 4 + 2];
   if (STEP == 2) {
     uint32_t c = 0;
-    for (uint32_t i0 = (uint32_t)c0 * kMCH; i0 < n; i0 += stride) {
-      const uint32_t i1 = min(n, i0 + (uint32_t)kMCH);
+    ranges([&](uint32_t i0, uint32_t i1) {
       for (uint32_t i = i0 + tid; i < i1; i += 256) c += (L[i].y >> 16) == T ? 1u : 0u;
-    }
+    });
     for (int o = 32; o > 0; o >>= 1) c += (uint32_t)__shfl_xor((int)c, o);
     if ((tid & 63) == 0 && c) atomicAdd(&a.eqtot[w], c);
     return;
   }
-  // STEP 3: values above T bid (x - T) + eps; of the values equal to T the first `need` in global job order
-  // (lsel: 0 none of this rank's, 1 all of them, 2 those with job <= J); the retention override; one packed
-  // {bid, ~worker} atomicMax per job as the sweep's bid kernel
+  // STEP 3: of the values equal to T the first `need` in global job order bid (lsel: 0 none of this rank's, 1 all
+  // of them, 2 those with job <= J)
   const uint32_t md = a.lsel[(int64_t)w * 4 + 1], J = a.lsel[(int64_t)w * 4];
-  const uint16_t eps = a.eps[0];
-  const _Float16 epsh = __builtin_bit_cast(_Float16, eps);
-  const _Float16 vT = __builtin_bit_cast(_Float16, okey_inv(T));
-  const bool ret = *a.round_dev < 100;
-  for (uint32_t i0 = (uint32_t)c0 * kMCH; i0 < n; i0 += stride) {
-    const uint32_t i1 = min(n, i0 + (uint32_t)kMCH);
-    for (uint32_t i = i0 + tid; i < i1; i += 256) {
-      const uint2 e = L[i];
-      const uint32_t j = e.x, k = e.y >> 16;
-      uint32_t bid = 0;
-      if (k > T) {
-        const _Float16 x = __builtin_bit_cast(_Float16, okey_inv(k));
-        bid = __builtin_bit_cast(uint16_t, (_Float16)((_Float16)(x - vT) + epsh));
-      } else if (k == T && (md == 1 || (md == 2 && j <= J))) {
-        bid = eps;
-      }
-      if (ret && a.hb[j] == w) bid = eps;  // retention: the previous winner bids eps on its job
-      if (bid) atomicMax(&a.key[j], (bid << 16) | (0xFFFFu - (uint32_t)w));
-    }
-  }
+  list_pass<3>(a, 0, w, L, kb, 0u, T, nullptr, ranges, [&](uint32_t j) { return md == 1 || (md == 2 && j <= J); });
 }
 
 // the selections from the summed list histograms (one wave per worker), and the round's global list verdict
@@ -2441,31 +2405,24 @@ __global__ __launch_bounds__(256) void da_list_select_kernel(SegAuction a) {
   uint32_t* h = a.hist + (int64_t)w * 256;
   uint32_t* sel = a.sel + (int64_t)w * 4;
   if (!LOW) {
-    uint32_t tot = h[4 * lane] + h[4 * lane + 1] + h[4 * lane + 2] + h[4 * lane + 3];
-    for (int o = 32; o > 0; o >>= 1) tot += (uint32_t)__shfl_xor((int)tot, o);
-    const bool bad = a.dmode[0] != kDList || a.hist[(int64_t)a.K * 256] != 0 || tot < jpw + 1 || sel[2] < a.lkb[w] ||
+    const ListSelHi hi = list_select_hi(h, jpw, lane);
+    const bool bad = a.dmode[0] != kDList || a.hist[(int64_t)a.K * 256] != 0 || !hi.ok || sel[2] < a.lkb[w] ||
                      *a.round_dev > 1000;
-    if (bad) {  // the slot turns void on every rank (each decides from the same reduced data)
-      if (lane == 0) {
+    if (lane == 0) {
+      if (bad) {  // the slot turns void on every rank (each decides from the same reduced data)
         a.dmode[0] = kDVoid;
         *a.lany = 0;
-      }
-    } else {
-      uint32_t b, above;
-      wave_select(h, jpw + 1, b, above);
-      if (lane == 0) {
-        sel[0] = b;
-        sel[1] = jpw + 1 - above;
-        sel[3] = above;
+      } else {  // (sel[1], sel[3]: the sweep selection's bookkeeping, rank in the bin and values above it)
+        sel[0] = hi.b1;
+        sel[1] = jpw + 1 - hi.above;
+        sel[3] = hi.above;
       }
     }
   } else {
-    uint32_t b, above;
-    wave_select(h, sel[1], b, above);
+    const ListSel s = list_select_lo(h, jpw, sel[0], sel[3]);
     if (lane == 0) {
-      const uint32_t T = (sel[0] << 8) | b;
-      sel[3] = jpw - (sel[3] + above);
-      sel[2] = T;
+      sel[3] = s.need;
+      sel[2] = s.T;
       a.eqtot[w] = 0;
     }
   }
@@ -2498,28 +2455,7 @@ __global__ __launch_bounds__(256) void da_list_rank_kernel(SegAuction a) {
       if ((e.y >> 16) == T && (shift == 24 || (e.x >> (shift + 8)) == J)) atomicAdd(&hst[(e.x >> shift) & 255u], 1u);
     }
     __syncthreads();
-    if (tid < 64) {  // ascending walk: the bin holding the rank-th smallest
-      const uint32_t h0 = hst[4 * tid], h1 = hst[4 * tid + 1], h2 = hst[4 * tid + 2], h3 = hst[4 * tid + 3];
-      const uint32_t own = h0 + h1 + h2 + h3;
-      uint32_t inc = own;
-      for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t y = (uint32_t)__shfl_up((int)inc, o);
-        if (tid >= o) inc += y;
-      }
-      const unsigned long long m = __ballot(inc >= rank);
-      const int Ln = m ? __ffsll((long long)m) - 1 : 63;
-      if (tid == Ln) {
-        uint32_t acc = inc - own;
-        const uint32_t hv[4] = {h0, h1, h2, h3};
-        int q = 0;
-        for (; q < 3; ++q) {
-          if (acc + hv[q] >= rank) break;
-          acc += hv[q];
-        }
-        sh[0] = (uint32_t)(4 * Ln + q);
-        sh[1] = rank - acc;
-      }
-    }
+    if (tid < 64) wave_rank_bin(hst, rank, tid, sh);
     __syncthreads();
     J = (J << 8) | sh[0];
     rank = sh[1];
@@ -2575,29 +2511,32 @@ __global__ void dauction_tables_kernel(int32_t* seg_off, int32_t* chunk_off, int
   chunk_off[1] = nch;
 }
 
+// one rank's share: one segment on the global-histogram path, no guessed pass
+AuctionShape dshape(int64_t n_local, int32_t k) { return {n_local, k, 1, cdiv(n_local, kCh), 1, false, true}; }
+
 int dstate(SegAuction& a, const uint16_t* scores, int32_t k, int64_t n_local, int64_t n_global, void* ws,
            int64_t wsb) {
   if (!scores && n_local > 0) return fail(RQSID_E_ARG, "dauction: null scores");
   if (k <= 1 || n_local < 0 || n_local > INT32_MAX || n_global < n_local || !ws)
     return fail(RQSID_E_ARG, "dauction: bad arguments (K=%d n_local=%lld n_global=%lld)", k, (long long)n_local,
                 (long long)n_global);
-  const int64_t nch = cdiv(n_local, kCh);
+  const AuctionShape shape = dshape(n_local, k);
+  const AuctionPlan plan = plan_auction(shape, read_auction_env());
+  const AuctionWorkspaceMap m(shape, plan);
+  if (wsb < m.total_bytes) return fail(RQSID_E_WORKSPACE, "dauction: workspace too small");
   a = SegAuction{};
   a.W = scores;
   a.K = k;
   a.S = 1;
-  a.total_chunks = nch;
+  a.total_chunks = shape.total_chunks;
   a.n_multi = 1;
   a.n_glob = n_global > 0 ? n_global : 1;
   char* p = (char*)ws;
-  a.seg_off = (const int32_t*)p;
-  a.chunk_off = (const int32_t*)(p + 64);
-  a.rounds = (int32_t*)(p + 128);
-  a.dmode = (uint32_t*)(p + 192);  // [0] slot mode (the caller may poll it), [1] sweep-slot flag
-  Carve c{p + kDHeader};
-  carve(a, c, n_local, k, 1, nch, false, true);
-  a.any_miss = a.dmode + 1;        // after carve (which clears it): the sweep kernels exit unless it is set
-  if (wsb < kDHeader + c.used) return fail(RQSID_E_WORKSPACE, "dauction: workspace too small");
+  a.seg_off = (const int32_t*)(p + m.seg_off);
+  a.chunk_off = (const int32_t*)(p + m.chunk_off);
+  a.rounds = (int32_t*)(p + m.rounds);
+  a.dmode = (uint32_t*)(p + m.dmode);  // [0] slot mode (the caller may poll it), [1] sweep-slot flag (any_miss)
+  carve(a, p, m, plan);
   return RQSID_OK;
 }
 
@@ -2606,42 +2545,33 @@ bool dvec(const uint16_t* scores, int64_t n_local) {
   return n_local % 4 == 0 && ((uintptr_t)scores & 7) == 0;
 }
 
-int64_t dws(int64_t n_local, int32_t k) {
-  SegAuction a{};
-  a.n_multi = 1;
-  Carve c{nullptr};
-  carve(a, c, n_local, k, 1, cdiv(n_local, kCh), false, true);
-  return kDHeader + c.used;
-}
 }  // namespace
 
 extern "C" {
 
 int64_t rqsid_dauction_workspace_bytes(int64_t n_local, int32_t n_workers) {
   if (n_local < 0 || n_workers <= 0) return -1;
-  return dws(n_local, n_workers);
+  const AuctionShape shape = dshape(n_local, n_workers);
+  return AuctionWorkspaceMap(shape, plan_auction(shape, read_auction_env())).total_bytes;
 }
 
 int rqsid_dauction_layout(int64_t n_local, int32_t n_workers, int64_t* offsets) {
   if (!offsets || n_local < 0 || n_workers <= 0) return fail(RQSID_E_ARG, "dauction_layout: bad arguments");
-  SegAuction a{};
-  a.n_multi = 1;
-  Carve c{(char*)nullptr + kDHeader};
-  carve(a, c, n_local, n_workers, 1, cdiv(n_local, kCh), false, true);
-  offsets[0] = (int64_t)((char*)a.mm - (char*)nullptr);     // u32 [2]: max key, min key
-  offsets[1] = (int64_t)((char*)a.hist - (char*)nullptr);   // u32 [K][256]
-  offsets[2] = (int64_t)((char*)a.eqtot - (char*)nullptr);  // u32 [K]
-  offsets[3] = (int64_t)((char*)a.have - (char*)nullptr);   // u32 [1]
-  offsets[4] = (int64_t)((char*)a.flag - (char*)nullptr);   // u8 [1]: bit 0 = still bidding
-  offsets[5] = 128;                                         // i32 [1]: rounds run (header, see dstate)
+  const AuctionShape shape = dshape(n_local, n_workers);
+  const AuctionWorkspaceMap m(shape, plan_auction(shape, read_auction_env()));
+  offsets[0] = m.mm;      // u32 [2]: max key, min key
+  offsets[1] = m.hist;    // u32 [K][256]
+  offsets[2] = m.eqtot;   // u32 [K]
+  offsets[3] = m.have;    // u32 [1]
+  offsets[4] = m.flag;    // u8 [1]: bit 0 = still bidding
+  offsets[5] = m.rounds;  // i32 [1]: rounds run (header)
   return RQSID_OK;
 }
 
 int rqsid_dauction_begin(const uint16_t* scores, int32_t n_workers, int64_t n_local, int64_t n_global,
                          int32_t* out_assign, void* workspace, int64_t workspace_bytes, void* stream) {
   SegAuction a;
-  int rc = dstate(a, scores, n_workers, n_local, n_global, workspace, workspace_bytes);
-  if (rc) return rc;
+  if (int rc = dstate(a, scores, n_workers, n_local, n_global, workspace, workspace_bytes)) return rc;
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(dauction_tables_kernel, dim3(1), dim3(1), 0, st, (int32_t*)a.seg_off, (int32_t*)a.chunk_off,
                      (int32_t)n_local, (int32_t)a.total_chunks);
@@ -2665,8 +2595,7 @@ int rqsid_dauction_begin(const uint16_t* scores, int32_t n_workers, int64_t n_lo
 int rqsid_dauction_eps(const uint16_t* scores, int32_t n_workers, int64_t n_local, int64_t n_global, void* workspace,
                        int64_t workspace_bytes, void* stream) {
   SegAuction a;
-  int rc = dstate(a, scores, n_workers, n_local, n_global, workspace, workspace_bytes);
-  if (rc) return rc;
+  if (int rc = dstate(a, scores, n_workers, n_local, n_global, workspace, workspace_bytes)) return rc;
   hipLaunchKernelGGL(sa_eps_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, a);
   return check_launch("dauction_eps");
 }
@@ -2675,17 +2604,14 @@ int rqsid_dauction_eps(const uint16_t* scores, int32_t n_workers, int64_t n_loca
 int rqsid_dauction_hist(const uint16_t* scores, int32_t n_workers, int64_t n_local, int64_t n_global, int32_t low,
                         void* workspace, int64_t workspace_bytes, void* stream) {
   SegAuction a;
-  int rc = dstate(a, scores, n_workers, n_local, n_global, workspace, workspace_bytes);
-  if (rc) return rc;
+  if (int rc = dstate(a, scores, n_workers, n_local, n_global, workspace, workspace_bytes)) return rc;
   if (n_local == 0) return RQSID_OK;
   const dim3 g((unsigned)a.total_chunks, (unsigned)cdiv(n_workers, kKG));
   hipStream_t st = (hipStream_t)stream;
   const bool vec = dvec(scores, n_local);
   // (each kernel exits at once unless the slot is its kind: sweep, or list)
-  if (low && vec) hipLaunchKernelGGL((sa_hist_kernel<1, true>), g, dim3(256), 0, st, a);
-  else if (low) hipLaunchKernelGGL((sa_hist_kernel<1, false>), g, dim3(256), 0, st, a);
-  else if (vec) hipLaunchKernelGGL((sa_hist_kernel<0, true>), g, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL((sa_hist_kernel<0, false>), g, dim3(256), 0, st, a);
+  if (low) launch_vec(vec, sa_hist_kernel<1, true>, sa_hist_kernel<1, false>, g, st, a);
+  else launch_vec(vec, sa_hist_kernel<0, true>, sa_hist_kernel<0, false>, g, st, a);
   const dim3 gl((unsigned)((int64_t)n_workers * a.dnb));
   if (low) hipLaunchKernelGGL((da_list_pass_kernel<1>), gl, dim3(256), 0, st, a);
   else hipLaunchKernelGGL((da_list_pass_kernel<0>), gl, dim3(256), 0, st, a);
@@ -2696,8 +2622,7 @@ int rqsid_dauction_hist(const uint16_t* scores, int32_t n_workers, int64_t n_loc
 int rqsid_dauction_select(const uint16_t* scores, int32_t n_workers, int64_t n_local, int64_t n_global, int32_t low,
                           void* workspace, int64_t workspace_bytes, void* stream) {
   SegAuction a;
-  int rc = dstate(a, scores, n_workers, n_local, n_global, workspace, workspace_bytes);
-  if (rc) return rc;
+  if (int rc = dstate(a, scores, n_workers, n_local, n_global, workspace, workspace_bytes)) return rc;
   const unsigned g = (unsigned)cdiv(n_workers, 4);
   hipStream_t st = (hipStream_t)stream;
   if (low) {
@@ -2714,8 +2639,7 @@ int rqsid_dauction_select(const uint16_t* scores, int32_t n_workers, int64_t n_l
 int rqsid_dauction_eqcount(const uint16_t* scores, int32_t n_workers, int64_t n_local, int64_t n_global,
                            void* workspace, int64_t workspace_bytes, void* stream) {
   SegAuction a;
-  int rc = dstate(a, scores, n_workers, n_local, n_global, workspace, workspace_bytes);
-  if (rc) return rc;
+  if (int rc = dstate(a, scores, n_workers, n_local, n_global, workspace, workspace_bytes)) return rc;
   hipStream_t st = (hipStream_t)stream;
   if (n_local == 0) {
     if (fill_async(a.eqtot, 0, (size_t)n_workers * 4, st) != hipSuccess)
@@ -2724,13 +2648,11 @@ int rqsid_dauction_eqcount(const uint16_t* scores, int32_t n_workers, int64_t n_
   }
   const dim3 g((unsigned)a.total_chunks, (unsigned)cdiv(n_workers, kKG));
   const bool vec = dvec(scores, n_local);
-  if (vec) hipLaunchKernelGGL((sa_eqcount_kernel<true>), g, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL((sa_eqcount_kernel<false>), g, dim3(256), 0, st, a);
+  launch_vec(vec, sa_eqcount_kernel<true>, sa_eqcount_kernel<false>, g, st, a);
   hipLaunchKernelGGL(sa_eqscan_kernel, dim3((unsigned)cdiv(n_workers, 4)), dim3(256), 0, st, a);
   // a sweep slot before the list phase builds the lists from this round's values (T is final here)
   hipLaunchKernelGGL(da_list_prep_kernel, dim3((unsigned)cdiv(n_workers, 256)), dim3(256), 0, st, a);
-  if (vec) hipLaunchKernelGGL((da_list_build_kernel<true>), g, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL((da_list_build_kernel<false>), g, dim3(256), 0, st, a);
+  launch_vec(vec, da_list_build_kernel<true>, da_list_build_kernel<false>, g, st, a);
   // a list slot counts its equal values from the lists
   hipLaunchKernelGGL((da_list_pass_kernel<2>), dim3((unsigned)((int64_t)n_workers * a.dnb)), dim3(256), 0, st, a);
   return check_launch("dauction_eqcount");
@@ -2740,14 +2662,12 @@ int rqsid_dauction_eqcount(const uint16_t* scores, int32_t n_workers, int64_t n_
 int rqsid_dauction_bid(const uint16_t* scores, int32_t n_workers, int64_t n_local, int64_t n_global,
                        const uint32_t* rank_off, void* workspace, int64_t workspace_bytes, void* stream) {
   SegAuction a;
-  int rc = dstate(a, scores, n_workers, n_local, n_global, workspace, workspace_bytes);
-  if (rc) return rc;
+  if (int rc = dstate(a, scores, n_workers, n_local, n_global, workspace, workspace_bytes)) return rc;
   if (n_local == 0) return RQSID_OK;
   a.rank_off = rank_off;
   const dim3 g((unsigned)a.total_chunks, (unsigned)cdiv(n_workers, kKG));
   hipStream_t st = (hipStream_t)stream;
-  if (dvec(scores, n_local)) hipLaunchKernelGGL((sa_bid_kernel<true>), g, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL((sa_bid_kernel<false>), g, dim3(256), 0, st, a);
+  launch_vec(dvec(scores, n_local), sa_bid_kernel<true>, sa_bid_kernel<false>, g, st, a);
   hipLaunchKernelGGL(da_list_rank_kernel, dim3((unsigned)n_workers), dim3(256), 0, st, a);
   hipLaunchKernelGGL((da_list_pass_kernel<3>), dim3((unsigned)((int64_t)n_workers * a.dnb)), dim3(256), 0, st, a);
   return check_launch("dauction_bid");
@@ -2757,8 +2677,7 @@ int rqsid_dauction_bid(const uint16_t* scores, int32_t n_workers, int64_t n_loca
 int rqsid_dauction_resolve(const uint16_t* scores, int32_t n_workers, int64_t n_local, int64_t n_global,
                            int32_t* out_assign, void* workspace, int64_t workspace_bytes, void* stream) {
   SegAuction a;
-  int rc = dstate(a, scores, n_workers, n_local, n_global, workspace, workspace_bytes);
-  if (rc) return rc;
+  if (int rc = dstate(a, scores, n_workers, n_local, n_global, workspace, workspace_bytes)) return rc;
   if (n_local == 0) return RQSID_OK;
   hipLaunchKernelGGL(sa_resolve_kernel, dim3((unsigned)a.total_chunks), dim3(256), 0, (hipStream_t)stream, a,
                      out_assign);
@@ -2769,8 +2688,7 @@ int rqsid_dauction_resolve(const uint16_t* scores, int32_t n_workers, int64_t n_
 int rqsid_dauction_end_round(const uint16_t* scores, int32_t n_workers, int64_t n_local, int64_t n_global,
                              void* workspace, int64_t workspace_bytes, void* stream) {
   SegAuction a;
-  int rc = dstate(a, scores, n_workers, n_local, n_global, workspace, workspace_bytes);
-  if (rc) return rc;
+  if (int rc = dstate(a, scores, n_workers, n_local, n_global, workspace, workspace_bytes)) return rc;
   hipLaunchKernelGGL(da_round_end_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, a);
   return check_launch("dauction_end_round");
 }
@@ -2799,8 +2717,7 @@ __global__ void da_debug_kernel(SegAuction a, uint32_t* out) {
 int rqsid_dauction_debug(const uint16_t* scores, int32_t n_workers, int64_t n_local, int64_t n_global, uint32_t* out,
                          void* workspace, int64_t workspace_bytes, void* stream) {
   SegAuction a;
-  int rc = dstate(a, scores, n_workers, n_local, n_global, workspace, workspace_bytes);
-  if (rc) return rc;
+  if (int rc = dstate(a, scores, n_workers, n_local, n_global, workspace, workspace_bytes)) return rc;
   hipLaunchKernelGGL(da_debug_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, a, out);
   return check_launch("dauction_debug");
 }
@@ -2812,8 +2729,7 @@ int rqsid_dauction_debug(const uint16_t* scores, int32_t n_workers, int64_t n_lo
 int rqsid_dauction_list_pass(const uint16_t* scores, int32_t n_workers, int64_t n_local, int64_t n_global, int32_t step,
                              const uint32_t* rank_off, void* workspace, int64_t workspace_bytes, void* stream) {
   SegAuction a;
-  int rc = dstate(a, scores, n_workers, n_local, n_global, workspace, workspace_bytes);
-  if (rc) return rc;
+  if (int rc = dstate(a, scores, n_workers, n_local, n_global, workspace, workspace_bytes)) return rc;
   if (step < -1 || step > 3) return fail(RQSID_E_ARG, "dauction_list_pass: step %d", step);
   hipStream_t st = (hipStream_t)stream;
   if (step == -1) {

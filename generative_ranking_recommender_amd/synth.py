@@ -54,6 +54,20 @@ def small_mixture(n: int, d: int = D_DEFAULT, m: int = 64, sigma: float = 0.25,
     return (means[lab] + np.float32(sigma) * rng.standard_normal((n, d), dtype=np.float32)).astype(np.float32)
 
 
+def auction_scores(n: int, k: int, levels: int = 0, seed: int = 0) -> np.ndarray:
+    """Worker-major fp16 auction scores [k][n] computed on the host.  levels 0: -distance of n unit rows (64-d
+    mixture) to k of them scaled by 0.9, the form of the training scores; levels L > 0: -(integers in 1..L) * 0.37,
+    thousands of equal values per worker."""
+    rng = np.random.default_rng([seed, n, k])
+    if levels:
+        return (-rng.integers(1, levels + 1, size=(k, n)).astype(np.float32) * np.float32(0.37)).astype(np.float16)
+    x = small_mixture(n, d=64, m=max(64, k), seed=seed + n)
+    x /= np.linalg.norm(x, axis=1, keepdims=True)
+    c = x[rng.choice(n, k, replace=n < k)] * np.float32(0.9)
+    d = np.sqrt(np.maximum((x ** 2).sum(1)[:, None] + (c ** 2).sum(1)[None] - 2 * x @ c.T, 0))
+    return np.ascontiguousarray((-d.T).astype(np.float16))
+
+
 def sha256(a: np.ndarray) -> str:
     return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
 

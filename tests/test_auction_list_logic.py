@@ -1,7 +1,8 @@
 """The list-round argument of auction_seg.hip (sa_list_round_kernel), checked on the host.
 
-A sweep round records, per worker, every job whose value key is >= its list base lkb = T_prev - 64 keys
-(T_prev: the worker's last threshold); a later round may take its threshold T (the (jpw+1)-th largest value),
+A sweep round records, per worker, every job whose value key is >= its list base lkb = T_prev - delta keys
+(T_prev: the worker's last threshold; the library's default margin is 32, RQSID_LIST_DELTA, and the argument
+holds for any margin: the simulation takes DELTA = 64); a later round may take its threshold T (the (jpw+1)-th largest value),
 its tie ranks and its bids from that list alone while T_prev >= lkb and >= jpw + 1 listed values are >= lkb,
 because values only fall between rounds except the previous winner's (its raw score), and a worker only wins
 a job it bid on from a listed value.  The simulation below runs the reference's auction (oracle fp16

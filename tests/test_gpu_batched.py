@@ -99,6 +99,32 @@ def test_seg_auction_small_groups_against_oracle(levels):
         assert np.array_equal(a[lay.off[s]:lay.off[s + 1]], np.asarray(want, dtype=np.int64)), s
 
 
+# [2051, 700, 1500, 5, 1027] x 8: three multi-chunk segments in one launch of 256-thread list blocks, lists of 1280
+# entries (walked from memory), 1004 and 768 (in registers), a one-chunk segment and one smaller than K: no list-only
+# blocks.  [1100, 1280, 1300] x 16: every segment multi-chunk, so list-only blocks run and the round ends by its
+# kernel; 1280 settles early.  [8003, 1100] x 8: a list above 4096 entries, so 1024-thread blocks, one list from memory
+# and one in registers
+@pytest.mark.parametrize("sizes,k", [([2051, 700, 1500, 5, 1027], 8), ([1100, 1280, 1300], 16), ([8003, 1100], 8)])
+def test_seg_auction_lists_equal_sweep(sizes, k, monkeypatch):
+    """Segmented list rounds (RQSID_AUCTION_LIST=1, the default) give the sweep's (=0) assignment and per-segment
+    round counts on distance scores of unit rows, and every segment of at most 2100 jobs the oracle's assignment of
+    its block."""
+    blocks = [synth.auction_scores(n, k, seed=s) for s, n in enumerate(sizes)]
+    flat = torch.from_numpy(np.concatenate([b.reshape(-1) for b in blocks])).to(DEV)
+    lay = ops.SegmentLayout(sizes, DEV)
+    out = {}
+    for mode in ("1", "0"):
+        monkeypatch.setenv("RQSID_AUCTION_LIST", mode)
+        a, rounds = ops.seg_auction(flat, k, lay)
+        out[mode] = (a.cpu().numpy(), rounds.cpu().numpy())
+    assert np.array_equal(out["1"][0], out["0"][0]) and np.array_equal(out["1"][1], out["0"][1])
+    for s, n in enumerate(sizes):
+        assert out["1"][1][s] == (0 if n < k else 1002 if n % k else out["0"][1][s])
+        if n <= 2100:
+            want = O.auction_lap_half(blocks[s].T.astype(np.float32), tie_rule="stable")
+            assert np.array_equal(out["1"][0][lay.off[s]:lay.off[s + 1]], np.asarray(want, dtype=np.int64)), s
+
+
 def test_seg_auction_repeat_calls_with_rewritten_scores():
     """Repeated auctions over one score buffer rewritten in place between calls (the K-Means iterations' pattern):
     the round blocks instantiated by one call are replayed by the next when the buffers and shapes agree, so

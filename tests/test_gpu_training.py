@@ -310,10 +310,11 @@ def _gpu_sharded_auction_worker(rank, world, port, w16, out):
 
 
 # per-rank shares of a multiple of 4 jobs take the 8-byte-load passes; 3002 (1501 per rank) the 2-byte ones;
-# N % K != 0 runs 1002 rounds, so the list phase (from round 32; 16 at K >= 1024) carries most of them
+# N % K != 0 runs 1002 rounds, so the list phase (from round 32; 16 at K >= 1024) carries most of them; 16006 (8003 per
+# rank) walks each worker's list with two blocks (dnb = 2), every other case with one
 @pytest.mark.parametrize("dlist", ["1", "0"])
 @pytest.mark.parametrize("n,k,levels", [(3000, 16, 7), (640, 64, 1000), (3002, 16, 7), (40001, 128, 0),
-                                        (24002, 1024, 0)])
+                                        (24002, 1024, 0), (16006, 16, 7)])
 def test_sharded_auction_gpu_passes_two_ranks(n, k, levels, dlist, monkeypatch):
     """Two ranks on one GPU (gloo collectives over device tensors), each running the rqsid_dauction_*
     passes on its row block: the concatenation equals the single-process GPU auction (pinned to the
@@ -373,22 +374,37 @@ def test_sharded_balanced_fit_world1(tmp_path):
         dist.destroy_process_group()
 
 
+# the K = 16 rows (scores made on the host, synth.auction_scores) take every form of the one-block list round in
+# about a thousand launch-bound rounds: 1603 and 1604, 256-thread blocks, 656-entry lists in registers, 2-byte and
+# 8-byte loads in the sweeps; 8003, 1024 threads, 2256 entries in registers; 16003, 4256 entries walked from memory;
+# "mb64" (RQSID_LIST_MB_JPW=64) the multi-block form with 3 entry chunks per worker, "tied3" on -(1..3) * 0.37, where
+# thousands of equal values meet its tie cap of 2048; 131203, the multi-block form by default (8200 jobs per worker)
 @pytest.mark.parametrize("n,k,half", [(200_000, 128, False), (100_000, 1280, True), (60_001, 1280, True),
-                                      (800_001, 128, True), (1_100_001, 128, False)])
+                                      (800_001, 128, True), (1_100_001, 128, False),
+                                      (1603, 16, "host"), (1604, 16, "host"), (8003, 16, "host"), (16003, 16, "host"),
+                                      (16003, 16, "host-mb64"), (16003, 16, "tied3-mb64"), (131203, 16, "host")])
 def test_auction_bid_list_equals_sweep(n, k, half, monkeypatch):
     """List rounds (auction_seg.hip sa_list_round_kernel: a worker's threshold, tie ranks and bids from the jobs a
-    sweep round listed, keys >= its threshold - 64, while the threshold stays above that base) give the sweep's
+    sweep round listed, keys >= its threshold - 32, while the threshold stays above that base) give the sweep's
     assignment and round count (RQSID_AUCTION_LIST=0) on the level-0 (K = 128) and candidate-fit (K = 1280,
     fp16 cdist) shapes, with the retention (round < 100) and leftover (round > 1000, N % K != 0) rules; above
     8192 jobs per worker (one segment) the default is the multi-block form (sa_mlist_*), checked against the
     sweep and the one-block form (RQSID_AUCTION_LIST=2); lists are built from round 32 on; the list rounds gather a
-    packed {winner, cost} word per listed job (RQSID_LIST_JS=0, mode "1s": the two arrays); times all (printed)."""
+    packed {winner, cost} word per listed job (RQSID_LIST_JS=0, mode "1s": the two arrays); times all (printed).
+    The host-made rows of at most 2000 jobs are also checked against the oracle (stable tie rule)."""
     import time
-    x = synth.small_mixture(n, m=3000, seed=k)
-    x /= np.linalg.norm(x, axis=1, keepdims=True)
-    xg = torch.from_numpy(x.astype(np.float32)).to(DEV)
-    c = xg[torch.from_numpy(np.random.default_rng(k).choice(n, k, replace=False)).to(DEV)] * 0.9
-    w = ops.auction_scores(xg, c, half=half)
+    w16 = None
+    if isinstance(half, str):
+        w16 = synth.auction_scores(n, k, levels=3 if half.startswith("tied3") else 0)
+        w = torch.from_numpy(w16).to(DEV)
+        if half.endswith("mb64"):
+            monkeypatch.setenv("RQSID_LIST_MB_JPW", "64")
+    else:
+        x = synth.small_mixture(n, m=3000, seed=k)
+        x /= np.linalg.norm(x, axis=1, keepdims=True)
+        xg = torch.from_numpy(x.astype(np.float32)).to(DEV)
+        c = xg[torch.from_numpy(np.random.default_rng(k).choice(n, k, replace=False)).to(DEV)] * 0.9
+        w = ops.auction_scores(xg, c, half=half)
     out = {}
     for mode in ("1", "1s", "0", "2"):
         monkeypatch.setenv("RQSID_AUCTION_LIST", mode[0])
@@ -406,6 +422,9 @@ def test_auction_bid_list_equals_sweep(n, k, half, monkeypatch):
     assert np.array_equal(out["2"][0], out["0"][0]) and out["2"][1] == out["0"][1]
     if n % k:
         assert out["1"][1] == 1002
+    if w16 is not None and n <= 2000:
+        want = O.auction_lap_half(w16.T.astype(np.float32), tie_rule="stable")
+        assert np.array_equal(out["1"][0], np.asarray(want, dtype=np.int64))
 
 
 def test_group_fits_k512_certified():
