@@ -22,7 +22,8 @@ SRCS = [PKG / "csrc" / "rqsid.hip", PKG / "csrc" / "assign.hip", PKG / "csrc" / 
         PKG / "csrc" / "assign_resident.hip", PKG / "csrc" / "assign_rows.hip", PKG / "csrc" / "assign_pc.hip",
         PKG / "csrc" / "auction.hip",
         PKG / "csrc" / "auction_seg.hip", PKG / "csrc" / "quant_error.hip", PKG / "csrc" / "assign_topk.hip",
-        PKG / "csrc" / "beam.hip", PKG / "csrc" / "silhouette.hip", PKG / "csrc" / "row_knn.hip"]
+        PKG / "csrc" / "beam.hip", PKG / "csrc" / "silhouette.hip", PKG / "csrc" / "row_knn.hip",
+        PKG / "csrc" / "id_cells.hip"]
 DEPS = SRCS + [PKG / "csrc" / "internal.h", PKG / "csrc" / "assign_common.h", PKG / "csrc" / "assign_plan.h",
                PKG / "csrc" / "topk_kernel.h", PKG / "csrc" / "exact_row.h", PKG / "csrc" / "tile_rows.h"]
 HEADER = REPO / "include" / "rqsid.h"
@@ -92,6 +93,10 @@ SIGNATURES = {
     "rqsid_row_knn_workspace_bytes": (c_i64, [c_i64, c_i32, c_i32, c_i32]),
     "rqsid_row_knn": (c_i32, [c_vp, c_i32, c_i64, c_i32, c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp,
                               c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "rqsid_id_cells_lds_rows": (c_i32, []),
+    "rqsid_id_cells_workspace_bytes": (c_i64, [c_i64, c_i32, c_i32]),
+    "rqsid_id_cells": (c_i32, [c_i64, c_vp, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                               c_vp, c_vp, c_i64, c_vp]),
     "rqsid_scale_groups": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp]),
     "rqsid_centroid_tile_rows": (c_i32, []),
     "rqsid_centroid_accumulate": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_i64, c_vp, c_vp]),

@@ -602,6 +602,37 @@ class RQEncoder:
         from .cluster_report import cluster_report
         return cluster_report(self, x, ids, **kw)
 
+    # ------------------------------------------------------------------ ID cells: collisions, unique IDs
+    def id_sizes(self) -> List[int]:
+        """Per level the exclusive upper bound of the IDs ``encode`` returns (the radices of the cell index)."""
+        sizes = [self.pcs[0].k] + [self.need[l] for l in range(1, self.L - 1)]
+        if self.L > 1:
+            remap = self._last_raw is not None and self.sem.remap_last
+            sizes.append(max(self._last_raw.count_max, 1) if remap else self.pcs[-1].k)
+        return sizes
+
+    def id_index(self, ids: torch.Tensor, rank_key: Optional[torch.Tensor] = None) -> "ops.IdCells":
+        """The cell index of ``ids`` [N, L] (``ops.id_cells`` with this encoder's level sizes): which rows share an
+        ID, each row's rank in its cell by ``rank_key`` (None: by row number), prefix ranges and counters."""
+        ids = ids.to(device=self.device, dtype=torch.int32).contiguous()
+        if ids.dim() != 2 or ids.shape[1] != self.L:
+            raise ValueError(f"ids must be [N, {self.L}], got {tuple(ids.shape)}")
+        return ops.id_cells(ids, self.id_sizes(), rank_key)
+
+    def unique_ids(self, x: torch.Tensor, ids: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """int32 [N, L + 1]: the semantic IDs of ``x`` (default ``encode(x)``) with one more token that makes every row
+        distinct: the row's rank among the rows that share its ID, by original-space reconstruction error
+        (``quant_error(x, ids).recon_err``; ties and NaN fall to row order), so token 0 is the row the ID describes
+        best.  Raises ValueError with ``residual_global_id=False``, as ``quant_error`` does."""
+        qe = self.quant_error(x, ids)
+        index = self.id_index(qe.ids, qe.recon_err.contiguous())
+        return torch.cat([qe.ids, index.rank.unsqueeze(1)], 1).contiguous()
+
+    def collision_report(self, x: torch.Tensor, ids: Optional[torch.Tensor] = None, **kw):
+        """Which IDs are shared and by how many rows: ``collision_report.collision_report(self, x, ids, **kw)``."""
+        from .collision_report import collision_report
+        return collision_report(self, x, ids, **kw)
+
     def decode(self, ids: torch.Tensor, err: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Reconstruction f32 [N, D] of semantic IDs (plain torch gathers).  Plain residuals: the sum of the levels'
         centres.  Normalised residuals: ``c0 + d0 (c1 + d1 c2)`` with ``d_l = err[:, l] + 1e-8`` from ``quant_error``

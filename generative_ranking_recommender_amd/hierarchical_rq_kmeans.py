@@ -1004,6 +1004,55 @@ class HierarchicalRQKMeans:
         x, _ = shard_rows(X, self.device, None)
         return neighbor_report(self._encoder(False), x, sample=sample, seed=seed, k=k, metric=metric)
 
+    def _single_process_rows(self, who: str, X: np.ndarray):
+        if not self.is_trained or not self.cluster_centers_list:
+            raise RuntimeError("Model not trained. Call train() first or load a trained model.")
+        if X.shape[1] != self.config.embedding_dim:
+            raise ValueError(f"Input dimension {X.shape[1]} does not match config embedding_dim "
+                             f"{self.config.embedding_dim}")
+        if self.group is not None:
+            raise NotImplementedError(f"{who}: the multi-GPU form is not built (single process only)")
+        from .quant_report import shard_rows
+        return shard_rows(X, self.device, None)[0]
+
+    def collision_report(self, X: np.ndarray, top: int = 5, members: int = 10) -> Dict:
+        """Which training-consistent IDs of ``X`` are shared, by how many rows, and how the ID space is used: the
+        figures of the reference's debug_collisions.py and analyze_semantic_ids.py (collision_report.py has the keys).
+        Keeps the cell index for ``find_rows_by_prefix``.  Single process only: with a process group it raises."""
+        x = self._single_process_rows("collision_report", X)
+        from .collision_report import collision_report
+        out, self._id_index = collision_report(self._encoder(False), x, top=top, members=members, return_index=True)
+        return out
+
+    def predict_unique(self, X: np.ndarray, ids: Optional[np.ndarray] = None) -> np.ndarray:
+        """int64 [N, L + 1]: ``predict(X, reference_quirks=False)`` (or the training-consistent ``ids`` [N, L] the
+        caller already holds) with one more token that makes every row's ID distinct, the row's rank by
+        reconstruction error among the rows that share its ID (``RQEncoder.unique_ids``).  Keeps the cell index for
+        ``find_rows_by_prefix``.  Single process only."""
+        x = self._single_process_rows("predict_unique", X)
+        L = len(self.config.layer_clusters)
+        if x.shape[0] == 0:
+            return np.zeros((0, L + 1), dtype=np.int64)
+        enc = self._encoder(False)
+        if ids is not None:
+            ids = torch.from_numpy(np.ascontiguousarray(ids, dtype=np.int32)).to(self.device)
+        qe = enc.quant_error(x, ids)
+        self._id_index = enc.id_index(qe.ids, qe.recon_err.contiguous())
+        return torch.cat([qe.ids, self._id_index.rank.unsqueeze(1)], 1).cpu().numpy().astype(np.int64)
+
+    def find_rows_by_prefix(self, prefix, limit: int = 10):
+        """``(count, rows)``: how many rows of the last ``collision_report`` / ``predict_unique`` call have an ID that
+        starts with ``prefix`` (1 .. L values), and the first ``limit`` of them in (ID, rank) order (int64 numpy):
+        the reference's ``find_songs_by_semantic_id`` (evaluate_semantic_ids.py) without the song names, by a
+        binary search over the cells instead of a scan over every row.  Single process only."""
+        if self.group is not None:
+            raise NotImplementedError("find_rows_by_prefix: the multi-GPU form is not built (single process only)")
+        index = getattr(self, "_id_index", None)
+        if index is None:
+            raise RuntimeError("find_rows_by_prefix: call collision_report(X) or predict_unique(X) first")
+        _, _, p0, p1 = index.prefix_range(prefix)
+        return p1 - p0, index.order[p0:min(p1, p0 + max(int(limit), 0))].cpu().numpy().astype(np.int64)
+
     def gather_ids(self, ids_local: torch.Tensor) -> torch.Tensor:
         """All ranks' IDs in row order (one variable-size all_gather of int32 rows)."""
         if self.group is None:

@@ -801,6 +801,184 @@ def row_knn(x: torch.Tensor, q: torch.Tensor, k: int, metric: str = "l2", order:
     return rows, val
 
 
+CELLS_FINE_MAX = 8192        # RQSID_CELLS_FINE_MAX
+CELLS_GROUPS_MAX = 1 << 24   # the wrapper's limit on the product of every level's size but the last
+CELLS_COUNTERS = 37
+ID_CELLS_WORD = ("bit 1: a row_index entry outside the rows was skipped; bit 2: a seg_row_off entry was clamped; "
+                 "bit 4: a last-level ID at or above its level's size (that row has rank / size / cell -1) "
+                 "(include/rqsid.h rqsid_id_cells)")
+
+
+def id_cells_lds_rows() -> int:
+    return int(lib().rqsid_id_cells_lds_rows())
+
+
+class IdCellsWorkspace:
+    """Scratch of rqsid_id_cells: per-group cell counts and bases, the sorted runs of cells beyond the LDS buffer, and
+    a 256-byte header zeroed here once: bytes [0, 4) the sticky error word, bytes [4, 152) the call's counters."""
+
+    def __init__(self, n_rows: int, n_groups: int, n_fine: int, device):
+        self.bytes = int(lib().rqsid_id_cells_workspace_bytes(n_rows, n_groups, n_fine))
+        if self.bytes < 0:
+            _lib.check(self.bytes, "rqsid_id_cells_workspace_bytes")
+        self.buf = torch.empty(max(self.bytes, 256), dtype=torch.uint8, device=device)
+        self.buf[:256].zero_()
+
+    def error_word(self) -> torch.Tensor:
+        return self.buf[:4].view(torch.int32)
+
+    def counters(self) -> torch.Tensor:
+        return self.buf[4:4 + 4 * CELLS_COUNTERS].view(torch.int32)
+
+
+def _prod(values) -> int:
+    out = 1
+    for v in values:
+        out *= int(v)
+    return out
+
+
+@dataclass
+class IdCells:
+    """What ``id_cells`` returns (device tensors; include/rqsid.h rqsid_id_cells).  By row: ``rank``, ``size``,
+    ``cell`` (-1 for a row whose ID names no cell); by position: ``order``; by cell: ``cell_off`` [capacity + 1],
+    ``cell_group``, ``cell_fine`` (the first ``n_cells`` entries are written); ``counters``: i32 [37] (n_cells, cells
+    of size >= 2, rows in them, cells of size 1, the largest cell, 32 bins of cells with size in [2^b, 2^(b+1)))."""
+    order: torch.Tensor
+    rank: torch.Tensor
+    size: torch.Tensor
+    cell: torch.Tensor
+    cell_off: torch.Tensor
+    cell_group: torch.Tensor
+    cell_fine: torch.Tensor
+    counters: torch.Tensor
+    sizes: tuple            # the levels' sizes the IDs were read with
+    invalid: torch.Tensor   # i64 scalar on the device: rows parked in the skipped group
+    _n_cells: Optional[int] = None
+    _keys: Optional[torch.Tensor] = None
+
+    @property
+    def n_cells(self) -> int:
+        """Number of non-empty cells (one host read, then cached)."""
+        if self._n_cells is None:
+            self._n_cells = int(self.counters[0].item())
+        return self._n_cells
+
+    @property
+    def n_invalid(self) -> int:
+        return int(self.invalid.item())
+
+    @property
+    def n_fine(self) -> int:
+        return self.sizes[-1] if len(self.sizes) > 1 else 1
+
+    def keys(self) -> torch.Tensor:
+        """The cells' IDs as mixed-radix numbers, i64 [n_cells], ascending."""
+        if self._keys is None:
+            n = self.n_cells
+            self._keys = self.cell_group[:n].long() * self.n_fine + self.cell_fine[:n].long()
+        return self._keys
+
+    def prefix_range(self, prefix):
+        """``(first cell, last cell, first position, last position)`` of the IDs that start with ``prefix`` (1 .. L
+        values): half-open ranges of cells and of ``order``; an absent prefix gives an empty range."""
+        prefix = [int(v) for v in prefix]
+        L = len(self.sizes)
+        if not 1 <= len(prefix) <= L:
+            raise ValueError(f"a prefix holds 1 .. {L} values, not {len(prefix)}")
+        if any(not 0 <= v < s for v, s in zip(prefix, self.sizes)):
+            return 0, 0, 0, 0
+        lo = 0
+        for v, s in zip(prefix, self.sizes):
+            lo = lo * s + v
+        below = _prod(self.sizes[len(prefix):])
+        keys = self.keys()
+        bounds = torch.tensor([lo * below, (lo + 1) * below], dtype=torch.int64, device=keys.device)
+        first, last = torch.searchsorted(keys, bounds).tolist()
+        p0, p1 = self.cell_off[torch.tensor([first, last], device=keys.device)].tolist()
+        return first, last, (p0 if last > first else p1), p1
+
+    def ids_of(self, cells) -> torch.Tensor:
+        """The ID tuples of cell numbers ``cells``: i32 [M, L]."""
+        cells = torch.as_tensor(cells, dtype=torch.int64, device=self.cell_group.device).reshape(-1)
+        g = self.cell_group[cells].long()
+        cols = [self.cell_fine[cells].long()] if len(self.sizes) > 1 else []
+        for s in reversed(self.sizes[:-1] if len(self.sizes) > 1 else self.sizes):
+            cols.append(g % s)
+            g = g // s
+        return torch.stack(cols[::-1], 1).to(torch.int32)
+
+
+def id_cells(ids: torch.Tensor, sizes: Optional[Sequence[int]] = None, rank_key: Optional[torch.Tensor] = None,
+             workspace: Optional[IdCellsWorkspace] = None, check: bool = True) -> IdCells:
+    """The cell index of semantic IDs (include/rqsid.h rqsid_id_cells): which rows share an ID, each row's place among
+    them by ``rank_key`` (f32 [N]; None: by row number), and the collision counters.
+
+    ``ids``: i32 [N, L]; ``sizes``: the levels' sizes (default: the per-level ``max + 1``, one host read).  The last
+    level is the fine ID (size <= CELLS_FINE_MAX), the mixed-radix number of the others the group key (product <=
+    2^24); with L = 1 level 0 is the group.  A row with a negative ID at any level, or with an ID at or above its
+    level's size in a group level, names no cell: it is parked in one extra skipped group (rank / size / cell -1,
+    after every cell in ``order``) and counted in ``n_invalid``.  A last-level ID at or above its size sets bit 4 of the
+    error word.  ``check``: read the error words after the call (one host sync) and raise RuntimeError if one is set."""
+    if ids.dim() != 2 or ids.shape[1] < 1 or ids.dtype != torch.int32:
+        raise ValueError("rqsid_id_cells: ids must be int32 [N, L]")
+    if ids.device.type != "cuda":
+        raise RuntimeError("rqsid kernels run on the GPU only: got a %s tensor" % ids.device.type)
+    _require_device(rank_key)
+    n, L = ids.shape
+    if rank_key is not None and (rank_key.dtype != torch.float32 or rank_key.numel() != n):
+        raise ValueError("rqsid_id_cells: rank_key must be float32 [N]")
+    if sizes is None:
+        sizes = [int(v) + 1 for v in ids.max(0).values.clamp_min(0).tolist()] if n else [1] * L
+    sizes = tuple(int(s) for s in sizes)
+    if len(sizes) != L or any(s < 1 for s in sizes):
+        raise ValueError(f"rqsid_id_cells: sizes must hold {L} positive values, got {sizes}")
+    group_sizes = sizes[:-1] if L > 1 else sizes
+    n_fine = sizes[-1] if L > 1 else 1
+    G = _prod(group_sizes)
+    if n_fine > CELLS_FINE_MAX:
+        raise ValueError(f"rqsid_id_cells: the last level's size {n_fine} exceeds {CELLS_FINE_MAX}")
+    if G > CELLS_GROUPS_MAX:
+        raise ValueError(f"rqsid_id_cells: the group levels' sizes multiply to {G} > 2^24")
+    dev = ids.device
+    cap = min(n, (G + 1) * n_fine)
+
+    def i32(m):
+        return torch.empty(m, dtype=torch.int32, device=dev)
+
+    if workspace is None or workspace.bytes < int(lib().rqsid_id_cells_workspace_bytes(n, G + 1, n_fine)):
+        workspace = IdCellsWorkspace(n, G + 1, n_fine, dev)
+    if n == 0:
+        return IdCells(i32(0), i32(0), i32(0), i32(0), torch.zeros(1, dtype=torch.int32, device=dev), i32(0), i32(0),
+                       torch.zeros(CELLS_COUNTERS, dtype=torch.int32, device=dev), sizes,
+                       torch.zeros((), dtype=torch.int64, device=dev), 0)
+    key = torch.zeros(n, dtype=torch.int64, device=dev)
+    bad = torch.zeros(n, dtype=torch.bool, device=dev)
+    for l, s in enumerate(group_sizes):
+        col = ids[:, l].long()
+        key = key * s + col
+        bad |= (col < 0) | (col >= s)
+    fine = None
+    if L > 1:
+        fine = ids[:, L - 1].contiguous()
+        bad |= fine < 0
+    key = torch.where(bad, G, key).to(torch.int32)
+    buckets = bucket(key, G + 1)
+    flags = torch.zeros(G + 1, dtype=torch.uint8, device=dev)
+    flags[G] = 1
+    out = IdCells(i32(n), i32(n), i32(n), i32(n), i32(cap + 1), i32(cap), i32(cap), workspace.counters(), sizes,
+                  bad.sum())
+    _lib.check(lib().rqsid_id_cells(n, _ptr(buckets.row_index), G + 1, _ptr(buckets.seg_row_off), _ptr(flags),
+                                    _ptr(fine), n_fine, _ptr(rank_key), _ptr(out.order), _ptr(out.rank),
+                                    _ptr(out.size), _ptr(out.cell), _ptr(out.cell_off), _ptr(out.cell_group),
+                                    _ptr(out.cell_fine), _ptr(workspace.buf), workspace.bytes, _stream()),
+               "rqsid_id_cells")
+    out.counters = workspace.counters().clone()  # the workspace may serve another call
+    if check:
+        check_error_words([buckets.error_word(), workspace.error_word()], "rqsid_id_cells", ID_CELLS_WORD)
+    return out
+
+
 def scale_groups(x: torch.Tensor, group_dims: Sequence[int], weights: Sequence[float]) -> torch.Tensor:
     _require_device(x)
     n, d = x.shape

@@ -32,8 +32,19 @@ class SemanticIDTrainer:
 
     def __init__(self, config, use_test_config: bool = False, device=None, group=None,
                  report_quantization: bool = False, report_margins: bool = False, report_beam: int = 0,
-                 report_clusters: int = 0, report_neighbors: int = 0):
+                 report_clusters: int = 0, report_neighbors: int = 0, report_collisions: bool = False,
+                 dedup_token: bool = False):
         self.config = config
+        # opt-in: also write collision_report.json (HierarchicalRQKMeans.collision_report of the training rows: the
+        # figures of the reference's debug_collisions.py and analyze_semantic_ids.py); dedup_token also writes
+        # song_semantic_ids_unique.jsonl, the training-consistent IDs with one more token (the row's rank among the
+        # rows that share its ID) so that every song's tuple is distinct.  Single process only: refused here,
+        # before any training.  song_semantic_ids.jsonl is written as ever
+        self.report_collisions = bool(report_collisions)
+        self.dedup_token = bool(dedup_token)
+        if group is not None and (self.report_collisions or self.dedup_token):
+            raise NotImplementedError("SemanticIDTrainer: report_collisions and dedup_token are single-process only "
+                                      "(the multi-GPU cell index is not built)")
         # opt-in (a sample size): also write neighbor_report.json (HierarchicalRQKMeans.neighbor_quality of the
         # training rows: how many of a row's exact nearest rows share its ID prefix, per depth).  Single process
         # only: refused here, before any training
@@ -126,6 +137,20 @@ class SemanticIDTrainer:
             neighbors = model.neighbor_quality(vectors, sample=self.report_neighbors)
             rq_io.write_json(str(self.output_dir / "neighbor_report.json"), neighbors)
             result["neighbor_report"] = neighbors
+        if self.report_collisions:
+            collisions = model.collision_report(vectors)
+            rq_io.write_json(str(self.output_dir / "collision_report.json"), collisions)
+            result["collision_report"] = collisions
+        if self.dedup_token:
+            # the trained IDs themselves (the tuples of song_semantic_ids.jsonl), each with its rank as one more token
+            trained = np.stack([np.asarray(t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else t)
+                                for t in train_result["cluster_ids"]], 1)
+            unique = model.predict_unique(vectors, ids=trained)
+            # the dict rule of _generate_semantic_ids: a song id repeated in the CSV keeps its last row's tuple
+            unique_ids = {sid: [int(v) for v in row] for sid, row in zip(song_ids, unique)}
+            path = Path(self.config.data.semantic_ids_file).with_name("song_semantic_ids_unique.jsonl")
+            rq_io.write_semantic_ids(str(path), unique_ids)
+            result["unique_semantic_ids"] = unique_ids
         return result
 
     def _generate_semantic_ids(self, song_ids: list, train_result: Dict) -> Dict:

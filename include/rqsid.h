@@ -420,6 +420,56 @@ int rqsid_row_knn(const void* x, int32_t x_format, int64_t n_rows, int32_t dim,
                   int32_t* out_row, float* out_val,
                   void* workspace, int64_t workspace_bytes, void* stream);
 
+/* The ID cell index: which rows share a full ID, each row's place among them, and the collision
+ * counters: the base of the reference's debug_collisions.py / analyze_semantic_ids.py figures, of
+ * evaluate_semantic_ids.py's find_songs_by_semantic_id and of a disambiguating last token.
+ * A cell is the set of rows with the same (group, fine ID).  Group g is the set of rows row_index[seg_row_off[g] ..
+ * seg_row_off[g+1]) (row_index NULL = identity; the output of rqsid_bucket over every level but the last serves as it
+ * is); fine_id[row] in [0, n_fine) is the last level (NULL: n_fine must be 1 and every group is one cell).
+ * Order inside a cell: ascending (key, row number), the key being rank_key[row] mapped to a total order (-0 taken as
+ * +0, every NaN after +inf); rank_key NULL: by row number alone.  The row number breaks every tie, so the output is a
+ * function of the row set alone: a permutation of row_index inside segments changes no output byte, and two calls give
+ * identical bytes.
+ * Outputs by row: out_rank (place in its cell), out_size (size of its cell), out_cell (its cell's number among the
+ * non-empty cells in (group, fine) order).  By position: out_order[n_rows], the rows in (group, fine, rank) order.  By
+ * cell j < n_cells (capacity min(n_rows, n_groups * n_fine), one more for cell_off): cell_off[j] the position in
+ * out_order where cell j starts, cell_off[n_cells] the end of the last cell (0 without cells), cell_group[j] and
+ * cell_fine[j] its ID; entries past n_cells are not written.  Cells come out in lexicographic ID order, so an ID prefix
+ * is a contiguous range of cells and of out_order.
+ * A group flagged RQSID_CELLS_GROUP_SKIP in group_flags (NULL: none) forms no cells: its rows get -1 in rank, size and
+ * cell, keep their row_index order in out_order and are counted nowhere.
+ * Workspace (rqsid_id_cells_workspace_bytes): bytes [0, 4) the sticky error word, zeroed by the caller once: 1 = a
+ * row_index entry outside [0, n_rows) (skipped; the group's span of out_order ends with one -1 per such entry), 2 = a
+ * seg_row_off entry outside [0, n_rows] or decreasing (clamped), 4 = a fine_id outside [0, n_fine): the row goes to an
+ * extra bin after its group's cells (in row order) and gets -1 / -1 / -1; no address is formed from the ID.  Bytes
+ * [4, 152) are 37 int32 counters zeroed by every call: n_cells, cells of size >= 2, rows in such cells, cells of size
+ * 1, the largest cell, and 32 bins counting the cells with size in [2^b, 2^(b+1)).
+ * Limits: n_rows < 2^31, 1 <= n_fine <= RQSID_CELLS_FINE_MAX; n_rows == 0 succeeds without touching anything.
+ * RQSID_E_ARG / RQSID_E_WORKSPACE before any HIP call.  Stream-ordered, no host synchronisation, graph-capturable.
+ * Integer atomics only (LDS histograms and the counters); no write takes its position from a device counter: the
+ * groups' cell counts are scanned by a kernel, and only the slot inside a cell's span comes from an LDS cursor, before
+ * the ranking fixes the final order.
+ * Method: per group an LDS histogram over the fine ID (groups of up to 1536 rows on one-wave blocks, up to 16384 on
+ * 256 threads, 1024 threads beyond; only the n_fine + 1 counters live in LDS, so groups are unbounded), a scan of the
+ * groups' cell counts, placement of the rows by cell into the workspace, then ranking per tile of 1024 positions, not
+ * per group: the (key bits, row) words of the cells that start in the tile are ranked in LDS, by counting up to 384
+ * rows and by a bitonic sort up to rqsid_id_cells_lds_rows(); a larger cell is sorted in runs of that size, written
+ * to the workspace, each element's rank being the sum of its lower bounds in the runs (rows x runs x 10 reads for
+ * one such cell, by one block: the price of a degenerate ID).
+ * Measured on an MI355X with rqsid_bucket in front, against a stable torch sort of (cell key << 32 | key bits) with
+ * unique_consecutive and the rank / size arithmetic (tools/id_cells_bench.py, profiles/id_cells_ab.json): 10M rows
+ * of the bench's encode, 75,752 cells, 1.73 ms against 2.63 ms; 6.25M rows over 65,536 groups x 512, 5.28M cells,
+ * 1.12 ms against 1.70 ms.  The tool's gate (at most half the composition's time) is NOT met: 0.66 at both shapes. */
+#define RQSID_CELLS_FINE_MAX 8192
+#define RQSID_CELLS_GROUP_SKIP 1u
+int32_t rqsid_id_cells_lds_rows(void);   /* largest cell ranked inside LDS in one piece */
+int64_t rqsid_id_cells_workspace_bytes(int64_t n_rows, int32_t n_groups, int32_t n_fine);
+int rqsid_id_cells(int64_t n_rows, const int32_t* row_index, int32_t n_groups, const int32_t* seg_row_off,
+                   const uint8_t* group_flags, const int32_t* fine_id, int32_t n_fine, const float* rank_key,
+                   int32_t* out_order, int32_t* out_rank, int32_t* out_size, int32_t* out_cell,
+                   int32_t* cell_off, int32_t* cell_group, int32_t* cell_fine,
+                   void* workspace, int64_t workspace_bytes, void* stream);
+
 /* y = x * w_g per dimension group (hierarchical_rq_kmeans.py:583-604). */
 int rqsid_scale_groups(const float* x, int64_t n, int32_t dim, const int32_t* group_dims,
                        int32_t n_groups, const float* weights, float* out, void* stream);
