@@ -23,9 +23,10 @@ SRCS = [PKG / "csrc" / "rqsid.hip", PKG / "csrc" / "assign.hip", PKG / "csrc" / 
         PKG / "csrc" / "auction.hip",
         PKG / "csrc" / "auction_seg.hip", PKG / "csrc" / "quant_error.hip", PKG / "csrc" / "assign_topk.hip",
         PKG / "csrc" / "beam.hip", PKG / "csrc" / "silhouette.hip", PKG / "csrc" / "row_knn.hip",
-        PKG / "csrc" / "id_cells.hip"]
+        PKG / "csrc" / "id_cells.hip", PKG / "csrc" / "probe_knn.hip"]
 DEPS = SRCS + [PKG / "csrc" / "internal.h", PKG / "csrc" / "assign_common.h", PKG / "csrc" / "assign_plan.h",
-               PKG / "csrc" / "topk_kernel.h", PKG / "csrc" / "exact_row.h", PKG / "csrc" / "tile_rows.h"]
+               PKG / "csrc" / "topk_kernel.h", PKG / "csrc" / "exact_row.h", PKG / "csrc" / "tile_rows.h",
+               PKG / "csrc" / "knn_core.h"]
 HEADER = REPO / "include" / "rqsid.h"
 # host-only I/O library (CSV reader): plain g++, no GPU code
 IO_LIB_PATH = PKG / "librqsid_io.so"
@@ -93,6 +94,9 @@ SIGNATURES = {
     "rqsid_row_knn_workspace_bytes": (c_i64, [c_i64, c_i32, c_i32, c_i32]),
     "rqsid_row_knn": (c_i32, [c_vp, c_i32, c_i64, c_i32, c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp,
                               c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "rqsid_probe_knn_workspace_bytes": (c_i64, [c_i64, c_i32, c_i32, c_i32]),
+    "rqsid_probe_knn": (c_i32, [c_vp, c_i32, c_i64, c_i32, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp,
+                                c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "rqsid_id_cells_lds_rows": (c_i32, []),
     "rqsid_id_cells_workspace_bytes": (c_i64, [c_i64, c_i32, c_i32]),
     "rqsid_id_cells": (c_i32, [c_i64, c_vp, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,

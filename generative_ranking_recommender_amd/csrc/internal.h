@@ -42,6 +42,26 @@ int seg_auction_run(const uint16_t* scores, int32_t n_workers, int32_t n_seg, co
                     const uint8_t* active, int32_t max_rounds, int32_t* out_assign, int32_t* out_rounds,
                     void* workspace, int64_t workspace_bytes, void* stream, bool vec, bool single_layout = false);
 
+// rqsid_bucket's workspace, in int32 words: counts [S] | cursor [S] | 64 words, the first the sticky error word |
+// for S <= 262144 the [B][S] count matrix and 2 cdiv(S, 64) block sums (rqsid.hip).  Here, not there, because an entry
+// that runs the bucketing inside its own workspace (probe_knn.hip) sizes that area from the same lines.
+constexpr int64_t kBucketMatrixWords = int64_t(1) << 22;
+inline int bucket_max_chunks(int64_t S) {
+  if (S <= 0 || S > 262144) return 0;
+  const int64_t b = kBucketMatrixWords / S < 256 ? kBucketMatrixWords / S : 256;
+  return (int)(b / 8 * 8);
+}
+inline int64_t bucket_workspace_words(int64_t S, int64_t B) {
+  return S * 2 + 64 + (B ? B * S + 2 * cdiv(S, 64) : 0);
+}
+inline int64_t bucket_error_word_at(int64_t S) { return 2 * S; }
+// enough for every key count up to S (S <= 262144): the matrix never exceeds min(256 S, kBucketMatrixWords) words,
+// and every other term grows with S
+inline int64_t bucket_workspace_words_up_to(int64_t S) {
+  const int64_t mat = 256 * S < kBucketMatrixWords ? 256 * S : kBucketMatrixWords;
+  return S * 2 + 64 + mat + 2 * cdiv(S, 64);
+}
+
 // exclusive-scan kernel shared by bucketing and the match-list builder (rqsid.hip)
 __global__ __launch_bounds__(1024) void bucket_scan_kernel(const int32_t* __restrict__ counts, int S, int tile_rows,
                                    int32_t* __restrict__ row_off, int32_t* __restrict__ tile_off,

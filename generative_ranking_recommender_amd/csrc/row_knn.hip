@@ -15,48 +15,14 @@
 //  3. knn_exact_kernel: one wave per query, lanes over dims; fp64 keys, eight rows at a time with the re-score's
 //     halving reduction, of the listed rows with s - e <= U and of every row of an uncertified chunk; ranked by
 //     (key, row number) in lanes 0 .. k-1.
+// The record, the policy of the screen, the fold of one query and the exact pass of one query live in knn_core.h,
+// which rqsid_probe_knn (probe_knn.hip) shares; here are the chunk geometry, the hull skip and the entry.
 // The result is a function of the row set alone: e, the slack and chunk_rows move only the amount of fp64 work.
 // No float atomics, no write positioned by a device counter.
-#include <hip/hip_runtime.h>
-
-#include <cfloat>
-#include <climits>
-#include <cmath>
-#include <cstdint>
-
-#include "assign_common.h"
-#include "exact_row.h"
-#include "tile_rows.h"
+#include "knn_core.h"
 
 namespace rqsid {
 namespace {
-
-// (the header's words [4, 16) are this entry's three counters)
-constexpr int kKnnSlack = 8;       // list entries beyond k
-constexpr int kKnnMV = kMaxDim / 4 / 64;  // float4 pieces of a row per lane of the exact pass
-constexpr int kKnnFull = 1, kKnnBad = 2, kKnnAllRows = 4;  // KnnMeta::flags
-
-// what a block knows about one query after its chunk, beside the list itself
-struct KnnMeta {
-  float max_s;    // the largest kept s (meaningful when full)
-  float xn_max;   // the largest |x|^2 among the chunk's rows the block met (L2: the worst-case e of the chunk)
-  int32_t count;  // list entries
-  int32_t flags;  // kKnnFull, kKnnBad (a non-finite s), kKnnAllRows (set by the fold: not certified)
-};
-static_assert(sizeof(KnnMeta) == 16, "record layout");
-
-// xn, qn: L2 fl32(|x|^2) (kNormSqFinite), cosine fl32(1 / |x|) (kNormInv); -1: never a neighbour / a query without
-// an answer
-struct KnnParams : RowPairParams {
-  double* U;      // [qtiles * kRowQ]
-  KnnMeta* meta;  // [n_chunks][qtiles * kRowQ]
-  float* ls;      // [n_chunks][C][qtiles * kRowQ]
-  int32_t* lr;    // likewise: row numbers
-  int32_t* out_row;
-  float* out_val;
-  int64_t nqp;    // qtiles * kRowQ
-  int32_t k, C;
-};
 
 // the positions query i searches
 __device__ __forceinline__ void query_range(const KnnParams& p, int i, int64_t& lo, int64_t& hi) {
@@ -65,93 +31,19 @@ __device__ __forceinline__ void query_range(const KnnParams& p, int i, int64_t& 
   hi = s >= 0 ? off_at(p, s + 1) : p.n_rows;
 }
 
-// e >= |s - t|, in fp64 from the stored fp32 norms: L2 (|q|^2 + |x|^2) R + dim 2^-120, cosine
-// R + 2^-50, R = 1.01 (dim + 8) 2^-24
-template <int METRIC>
-__device__ __forceinline__ double knn_err(int dim, float qn, float xn) {
-  const double R = 1.01 * (double)(dim + 8) * 0x1p-24;
-  if constexpr (METRIC == RQSID_KNN_L2) return ((double)qn + (double)xn) * R + (double)dim * 0x1p-120;
-  return R + 0x1p-50;
-}
-
-// row_tile_sweep's policy: screen values, and per query the C smallest of the chunk
-template <int METRIC>
-struct KnnPolicy {
+// knn_core.h's accessor: query i's lists are its chunks', [n_chunks][C][nqp]
+struct ChunkLists {
   const KnnParams& p;
-  // MFMA role: lane (r, h) of wave wv holds query q0 + 32 wv + r, its norm term, self row and range
-  float qn;
-  int self;
+  int i;
   int64_t qlo, qhi;
-  // walking role (threads 0..127): query q0 + t and its list in the workspace
-  float* ls;
-  int32_t* lr;
-  int cnt, bad;
-  float thr;  // what a value has to stay below to enter: +inf until the list is full, then its largest
-  float mx;
-  float xmax;  // L2: the largest |x|^2 this thread met
-
-  __device__ __forceinline__ void tile_row(int, int& row, float& xn) {
-    if (xn < 0.f) row = -1;  // a row without a key is never a neighbour
-    if (METRIC == RQSID_KNN_L2 && row >= 0) xmax = fmaxf(xmax, xn);
-  }
-
-  __device__ __forceinline__ float value(int64_t pos0, int j, float dot, float xn, int rw) const {
-    // the query's range in positions of this tile
-    const int jlo = qlo - pos0 > 0 ? (qlo - pos0 < kRowTile ? (int)(qlo - pos0) : kRowTile) : 0;
-    const int jhi = qhi - pos0 > 0 ? (qhi - pos0 < kRowTile ? (int)(qhi - pos0) : kRowTile) : 0;
-    float s;
-    if constexpr (METRIC == RQSID_KNN_L2) s = fmaf(-2.0f, dot, qn + xn);
-    else s = -((dot * qn) * xn);
-    // a value the interval does not cover becomes -inf: it reaches the walk, which flags the chunk
-    s = fabsf(s) <= FLT_MAX ? s : -INFINITY;
-    const bool skip = (rw < 0) | (rw == self) | (j < jlo) | (j >= jhi);
-    return skip ? INFINITY : s;
-  }
-
-  __device__ __forceinline__ void walk(int64_t, const float* s_d, const int* s_row) {
-    const int t = threadIdx.x;
-    for (int j = 0; j < kRowTile; j += 8) {
-      float v[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) v[u] = s_d[(j + u) * kRowDStride + t];
-      bool any = false;
-#pragma unroll
-      for (int u = 0; u < 8; ++u) any |= v[u] < thr;
-      if (any) {
-#pragma unroll 1
-        for (int u = 0; u < 8; ++u) {
-          const float w = s_d[(j + u) * kRowDStride + t];
-          if (!(w < thr)) continue;
-          if (w == -INFINITY) {
-            bad = 1;
-            continue;
-          }
-          const int row = s_row[j + u];
-          if (cnt < p.C) {
-            ls[cnt * p.nqp] = w;
-            lr[cnt * p.nqp] = row;
-            mx = fmaxf(mx, w);
-            if (++cnt == p.C) thr = mx;
-          } else {  // replace the largest; the new largest is the second largest or the newcomer
-            int im = 0;
-            float m1 = -INFINITY, m2 = -INFINITY;
-            for (int i = 0; i < p.C; ++i) {
-              const float a = ls[i * p.nqp];
-              if (a > m1) {
-                m2 = m1;
-                m1 = a;
-                im = i;
-              } else if (a > m2) {
-                m2 = a;
-              }
-            }
-            ls[im * p.nqp] = w;
-            lr[im * p.nqp] = row;
-            thr = fmaxf(m2, w);
-          }
-        }
-      }
-    }
+  __device__ __forceinline__ int n() const { return p.n_chunks; }
+  __device__ __forceinline__ int64_t meta_at(int c) const { return (int64_t)c * p.nqp + i; }
+  __device__ __forceinline__ int64_t entry_at(int c, int j) const { return ((int64_t)c * p.C + j) * p.nqp + i; }
+  __device__ __forceinline__ void range(int c, int64_t& a, int64_t& b) const {
+    const int64_t c0 = (int64_t)c * p.chunk_rows;
+    const int64_t c1 = c0 + p.chunk_rows < p.n_rows ? c0 + p.chunk_rows : p.n_rows;
+    a = c0 > qlo ? c0 : qlo;
+    b = c1 < qhi ? c1 : qhi;
   }
 };
 
@@ -217,46 +109,7 @@ template <int METRIC>
 __global__ __launch_bounds__(256) void knn_fold_kernel(KnnParams p) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= p.nq) return;
-  const float qn = p.qn[i];
-  if (qn < 0.f) {  // no answer: the exact pass writes -1 / NaN
-    atomicAdd(reinterpret_cast<int*>(p.err) + 3, 1);
-    return;
-  }
-  // the k smallest s + e, unsorted slots k .. 15 held at -inf so that they never take part
-  double top[RQSID_KNN_MAX];
-#pragma unroll
-  for (int j = 0; j < RQSID_KNN_MAX; ++j) top[j] = j < p.k ? INFINITY : -INFINITY;
-  for (int c = 0; c < p.n_chunks; ++c) {
-    const int cnt = p.meta[(int64_t)c * p.nqp + i].count;
-    for (int j = 0; j < cnt; ++j) {
-      const int64_t at = ((int64_t)c * p.C + j) * p.nqp + i;
-      const float s = p.ls[at];
-      double v = (double)s + knn_err<METRIC>(p.dim, qn, METRIC == RQSID_KNN_L2 ? p.xn[p.lr[at]] : 0.f);
-#pragma unroll
-      for (int jj = 0; jj < RQSID_KNN_MAX; ++jj) {
-        const double o = top[jj];
-        const bool lt = v < o;
-        top[jj] = lt ? v : o;
-        v = lt ? o : v;
-      }
-    }
-  }
-  double U = -INFINITY;
-#pragma unroll
-  for (int j = 0; j < RQSID_KNN_MAX; ++j) U = top[j] > U ? top[j] : U;
-  p.U[i] = U;
-  int all_rows = 0;
-  for (int c = 0; c < p.n_chunks; ++c) {
-    KnnMeta* const m = p.meta + (int64_t)c * p.nqp + i;
-    const int fl = m->flags;
-    const bool beyond = (double)m->max_s - knn_err<METRIC>(p.dim, qn, m->xn_max) > U;
-    if ((fl & kKnnBad) || ((fl & kKnnFull) && !beyond)) {
-      m->flags = fl | kKnnAllRows;
-      ++all_rows;
-    }
-  }
-  if (all_rows) atomicAdd(reinterpret_cast<int*>(p.err) + 2, all_rows);
-  else atomicAdd(reinterpret_cast<int*>(p.err) + 1, 1);
+  knn_fold_query<METRIC>(p, i, ChunkLists{p, i, 0, 0});
 }
 
 // one wave per query: fp64 keys of the rows that can still place, ranked by (key, row) in lanes 0 .. k-1
@@ -265,126 +118,9 @@ __global__ __launch_bounds__(256) void knn_exact_kernel(KnnParams p) {
   const int lane = threadIdx.x & 63;
   const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (i >= p.nq) return;
-  const float qn = p.qn[i];
-  if (qn < 0.f) {
-    if (lane < p.k) {
-      p.out_row[(int64_t)i * p.k + lane] = -1;
-      p.out_val[(int64_t)i * p.k + lane] = __uint_as_float(0x7FC00000u);
-    }
-    return;
-  }
-  const int nv = p.dim / 4;
-  const float* const xf = static_cast<const float*>(p.x);
-  float4 v[kKnnMV];
-  double qq = 0.0;
-#pragma unroll
-  for (int m = 0; m < kKnnMV; ++m) {
-    const int e = lane + 64 * m;
-    v[m] = e < nv ? load_row4<XF>(static_cast<const float*>(p.q), i, p.dim, e) : make_float4(0.f, 0.f, 0.f, 0.f);
-    qq += sq4(v[m]);
-  }
-  const double sqq = sqrt(wave_sum(qq));
-  const double U = p.U[i];
-  const int self = clean_self(p, i);
-  int64_t qlo, qhi;
-  query_range(p, i, qlo, qhi);
-
-  double hk = INFINITY;  // lane j < k: the j-th place so far
-  int hr = INT_MAX;
-  // the fp64 keys of up to eight rows (rr < 0: none), each offered to the ranking
-  const auto batch = [&](const int (&rr)[kBatch]) __attribute__((always_inline)) {
-    double a0[kBatch], a1[kBatch];
-#pragma unroll
-    for (int jj = 0; jj < kBatch; ++jj) {
-      a0[jj] = a1[jj] = 0.0;
-#pragma unroll
-      for (int m = 0; m < kKnnMV; ++m) {
-        const int e = lane + 64 * m;
-        if (rr[jj] < 0 || e >= nv) continue;
-        const float4 c = load_row4<XF>(xf, rr[jj], p.dim, e);
-        if constexpr (METRIC == RQSID_KNN_L2) {
-          const double d0 = (double)v[m].x - c.x, d1 = (double)v[m].y - c.y, d2 = (double)v[m].z - c.z,
-                       d3 = (double)v[m].w - c.w;
-          a0[jj] = fma(d3, d3, fma(d2, d2, fma(d1, d1, fma(d0, d0, a0[jj]))));
-        } else {
-          a0[jj] = fma((double)v[m].w, (double)c.w, fma((double)v[m].z, (double)c.z,
-                   fma((double)v[m].y, (double)c.y, fma((double)v[m].x, (double)c.x, a0[jj]))));
-          a1[jj] = fma((double)c.w, (double)c.w, fma((double)c.z, (double)c.z,
-                   fma((double)c.y, (double)c.y, fma((double)c.x, (double)c.x, a1[jj]))));
-        }
-      }
-    }
-    double key = batch_reduce<64>(a0, lane);
-    if constexpr (METRIC == RQSID_KNN_COSINE) key = -(key / (sqq * sqrt(batch_reduce<64>(a1, lane))));
-#pragma unroll
-    for (int jj = 0; jj < kBatch; ++jj) {
-      if (rr[jj] < 0) continue;
-      const double ck = __shfl(key, batch_lane<64>(jj));
-      const int cr = rr[jj];
-      if (!(fabs(ck) <= DBL_MAX)) continue;  // a row with a non-finite key is never a neighbour
-      const bool before = lane < p.k && (hk < ck || (hk == ck && hr < cr));
-      const int at = __popcll(__ballot(before));  // (the places are sorted: the better ones are lanes 0 .. at-1)
-      if (at >= p.k) continue;
-      const double uk = __shfl_up(hk, 1);
-      const int ur = __shfl_up(hr, 1);
-      if (lane == at) {
-        hk = ck;
-        hr = cr;
-      } else if (lane > at && lane < p.k) {
-        hk = uk;
-        hr = ur;
-      }
-    }
-  };
-  // the rows of the lanes named in mask (wave-uniform), eight at a time
-  const auto offer = [&](uint64_t mask, int row) __attribute__((always_inline)) {
-    while (mask) {
-      int rr[kBatch];
-#pragma unroll
-      for (int jj = 0; jj < kBatch; ++jj) {
-        rr[jj] = -1;
-        if (mask) {
-          rr[jj] = __shfl(row, __builtin_ctzll(mask));
-          mask &= mask - 1;
-        }
-      }
-      batch(rr);
-    }
-  };
-
-  for (int c = 0; c < p.n_chunks; ++c) {
-    const KnnMeta m = p.meta[(int64_t)c * p.nqp + i];
-    if (!(m.flags & kKnnAllRows)) {
-      for (int j0 = 0; j0 < m.count; j0 += 64) {
-        const int j = j0 + lane;
-        bool ok = j < m.count;
-        int row = -1;
-        if (ok) {
-          const int64_t at = ((int64_t)c * p.C + j) * p.nqp + i;
-          row = p.lr[at];
-          ok = (double)p.ls[at] - knn_err<METRIC>(p.dim, qn, METRIC == RQSID_KNN_L2 ? p.xn[row] : 0.f) <= U;
-        }
-        offer(__ballot(ok), row);
-      }
-    } else {
-      const int64_t c0 = (int64_t)c * p.chunk_rows;
-      const int64_t c1 = c0 + p.chunk_rows < p.n_rows ? c0 + p.chunk_rows : p.n_rows;
-      const int64_t a = c0 > qlo ? c0 : qlo, b = c1 < qhi ? c1 : qhi;
-      for (int64_t pos = a; pos < b; pos += 64) {
-        const int64_t pp = pos + lane;
-        int row = -1;
-        if (pp < b) row = p.row_index ? p.row_index[pp] : (int)pp;
-        const bool ok = pp < b && (int64_t)(uint32_t)row < p.n_rows && row != self;
-        offer(__ballot(ok), row);
-      }
-    }
-  }
-  if (lane < p.k) {
-    const bool none = hr == INT_MAX;
-    p.out_row[(int64_t)i * p.k + lane] = none ? -1 : hr;
-    p.out_val[(int64_t)i * p.k + lane] =
-        none ? INFINITY : (METRIC == RQSID_KNN_L2 ? (float)sqrt(hk) : (float)(-hk));
-  }
+  ChunkLists L{p, i, 0, 0};
+  query_range(p, i, L.qlo, L.qhi);
+  knn_exact_query<XF, METRIC>(p, i, lane, L);
 }
 
 struct KnnPlan : RowPairPlan {
@@ -402,11 +138,6 @@ bool knn_plan(int64_t n_rows, int32_t nq, int32_t k, int32_t chunk_rows, KnnPlan
   pl.off_lr = pl.off_ls + up256(pl.n_chunks * pl.nqp * pl.C * 4);
   pl.bytes = pl.off_lr + up256(pl.n_chunks * pl.nqp * pl.C * 4);
   return ok;
-}
-
-int knn_check_k(const char* who, int32_t k) {
-  if (k < 1 || k > RQSID_KNN_MAX) return fail(RQSID_E_ARG, "%s: k = %d (1 .. %d)", who, k, RQSID_KNN_MAX);
-  return RQSID_OK;
 }
 
 template <int XF, int METRIC>
@@ -449,9 +180,7 @@ int rqsid_row_knn(const void* x, int32_t x_format, int64_t n_rows, int32_t dim, 
                   int32_t* out_row, float* out_val, void* workspace, int64_t workspace_bytes, void* stream) {
   const char* const who = "rqsid_row_knn";
   int rc;
-  if ((rc = row_pair_check_format(who, x_format, dim))) return rc;
-  if (metric != RQSID_KNN_L2 && metric != RQSID_KNN_COSINE)
-    return fail(RQSID_E_ARG, "%s: unknown metric %d", who, metric);
+  if ((rc = row_pair_check_format(who, x_format, dim)) || (rc = knn_check_metric(who, metric))) return rc;
   if ((rc = row_pair_check_counts(who, n_rows, n_queries)) || (rc = knn_check_k(who, k)) ||
       (rc = row_pair_check_chunks(who, chunk_rows, n_segments)))
     return rc;

@@ -188,14 +188,10 @@ __global__ __launch_bounds__(256) void bucket_scatter_kernel(const int32_t* __re
 // scan; the LDS-histogram form flushes ~S global atomics per block.  Blocks of one chunk share an XCD (B is a
 // multiple of 8) and so its keys; 1024 threads with kBucketUnroll keys in flight each hide the load latency of
 // the few blocks (B x slices).
-constexpr int64_t kBucketMatrixWords = int64_t(1) << 22;
 constexpr int kBucketUnroll = 8;
 // chunks of the count matrix for S keys (S <= 262144; more keys take the global-atomic form): at most
-// bucket_max_chunks(S) (the workspace's matrix), and ~32K rows per chunk for small inputs (at least 8 chunks), so
-// the column scan of a 100k-row call reads 8 rows of the matrix, not 256
-inline int bucket_max_chunks(int S) {
-  return S > 262144 ? 0 : (int)std::min<int64_t>(256, kBucketMatrixWords / S) / 8 * 8;
-}
+// bucket_max_chunks(S) (internal.h: the workspace's matrix), and ~32K rows per chunk for small inputs (at least 8
+// chunks), so the column scan of a 100k-row call reads 8 rows of the matrix, not 256
 inline int bucket_chunks(int64_t n, int S) {
   if (n <= 0) return 0;
   const int64_t want = std::max<int64_t>(8, cdiv(n, 32768) / 8 * 8);
@@ -779,8 +775,7 @@ int32_t rqsid_centroid_tile_rows(void) { return kAccTileRows; }
 // (B x S <= 4M words: 16 MiB, independent of n so that one workspace serves every call with these keys)
 int64_t rqsid_bucket_workspace_bytes(int64_t n, int32_t n_segments) {
   (void)n;
-  const int64_t B = bucket_max_chunks(n_segments);
-  return ((int64_t)n_segments * 2 + 64 + (B ? B * n_segments + 2 * cdiv(n_segments, 64) : 0)) * 4;
+  return bucket_workspace_words(n_segments, bucket_max_chunks(n_segments)) * 4;
 }
 
 int rqsid_bucket(const int32_t* keys, int64_t n, int32_t S, int32_t tile_rows, int32_t* seg_row_off,
@@ -811,7 +806,7 @@ int rqsid_bucket(const int32_t* keys, int64_t n, int32_t S, int32_t tile_rows, i
     hipLaunchKernelGGL(bucket_chunk_offsets_kernel, dim3(nblk), dim3(64), 0, st, counts, bsum, S, tile_rows,
                        seg_row_off, seg_tile_off);
     hipLaunchKernelGGL(bucket_chunk_scatter_kernel, grid, dim3(1024), lds, st, keys, n, S, chunk_rows, mat,
-                       seg_row_off, row_index, cursor + S);
+                       seg_row_off, row_index, counts + bucket_error_word_at(S));
     return check_launch("bucket_chunk");
   }
   if (fill_async(counts, 0, (size_t)S * 4, st) != hipSuccess) return fail(RQSID_E_LAUNCH, "bucket: memset");
@@ -834,7 +829,7 @@ int rqsid_bucket(const int32_t* keys, int64_t n, int32_t S, int32_t tile_rows, i
   if (n > 0) {
     const unsigned blocks = S <= kBucketLdsBins ? (unsigned)cdiv(n, scat_rows) : grid_cap(cdiv(n, 256 * 16), 2048);
     hipLaunchKernelGGL(bucket_scatter_kernel, dim3(blocks), dim3(256), lds, st, keys, n, S, cursor, seg_row_off,
-                       row_index, cursor + S, (int64_t)scat_rows);
+                       row_index, counts + bucket_error_word_at(S), (int64_t)scat_rows);
     if ((rc = check_launch("bucket_scatter"))) return rc;
   }
   return RQSID_OK;

@@ -1,4 +1,5 @@
-// tile_rows.h — the row-against-row block that silhouette.hip and row_knn.hip share.  Not ABI.
+// tile_rows.h — the row-against-row block that silhouette.hip, row_knn.hip and probe_knn.hip share.
+// Not ABI.
 //
 // A block owns 128 queries and a run of 128-position tiles of the bucketed order (row_index).  Per tile and 32-dim
 // chunk it stages fp32 images of the 128 base rows and of its 128 queries in LDS (144-B pitch, 16-bit rows widened
@@ -41,6 +42,8 @@ struct RowPairParams {
   const int32_t* seg_off;     // null: no segments (n_seg = 0)
   const int32_t* query_self;
   const int32_t* query_seg;
+  const int32_t* q_row;       // null: column c of the blocks is row c of q; else row q_row[c], -1: none (the
+                              // caller's own table, [qtiles * kRowQ], with every entry inside [-1, nq))
   float* xn;      // [n_rows] the row's norm term, by row (NormRule)
   float* qn;      // [qtiles * kRowQ] likewise
   uint32_t* err;  // the header: the sticky error word, then the entry's counters
@@ -185,9 +188,8 @@ __device__ __forceinline__ RowTileLds row_tile_lds() {
   return {s_buf, s_row, s_xn};
 }
 
-// Tiles [tile0, tile1) of the chunk [c0, c1) of positions against the block's 128 queries, q0 .. q0 + 127.  The
-// policy supplies
-// what the callers differ in, as inlined hooks:
+// Tiles [tile0, tile1) of the chunk [c0, c1) of positions against the block's 128 queries, columns q0 .. q0 + 127
+// (rows of q, or through RowPairParams::q_row).  The policy supplies what the callers differ in, as inlined hooks:
 //   tile_row(t, row, xn)          thread t < 128, before the tile's MFMAs: the row number (-1: none) and norm term
 //                                 of position t of the tile, which it may change;
 //   value(pos0, j, dot, xn, row)  the float that is parked for the lane's query against position j of the tile;
@@ -204,7 +206,10 @@ __device__ __forceinline__ void row_tile_sweep(const RowPairParams& p, int q0, i
   const int f4 = t & 7, srow = t >> 3;
   int my_q[4];
 #pragma unroll
-  for (int i = 0; i < 4; ++i) my_q[i] = q0 + srow + 32 * i < p.nq ? q0 + srow + 32 * i : -1;
+  for (int i = 0; i < 4; ++i) {
+    const int c = q0 + srow + 32 * i;
+    my_q[i] = p.q_row ? p.q_row[c] : (c < p.nq ? c : -1);
+  }
   // the base row at a position of this chunk, or -1 (no address is formed from an entry outside [0, n_rows))
   auto row_at = [&](int64_t pos) {
     int row = -1;
@@ -374,6 +379,7 @@ inline void row_pair_fill(RowPairParams& p, const void* x, int64_t n_rows, int32
   p.seg_off = seg_off;
   p.query_self = query_self;
   p.query_seg = query_seg;
+  p.q_row = nullptr;
   p.xn = reinterpret_cast<float*>(ws + pl.off_xn);
   p.qn = reinterpret_cast<float*>(ws + pl.off_qn);
   p.err = reinterpret_cast<uint32_t*>(ws);

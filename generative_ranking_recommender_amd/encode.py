@@ -82,6 +82,15 @@ class Beam:
     slot: torch.Tensor       # i32 [N]: the slot ``ids`` came from
 
 
+@dataclass
+class IndexSearch:
+    """What ``RQEncoder.search`` returns (device tensors)."""
+    rows: torch.Tensor      # i32 [M, k]: the nearest rows among those under the probed prefixes, -1 past their end
+    val: torch.Tensor       # f32 [M, k]: distance or cosine similarity
+    scanned: torch.Tensor   # i32 [M]: catalogue positions read
+    prefixes: torch.Tensor  # i32 [M, probes, depth]: the probed ID prefixes (-1: a dead slot)
+
+
 class _TopKLevels:
     """Collects rqsid_assign_topk's outputs level by level while an encode runs (RQEncoder.encode_topk)."""
 
@@ -289,19 +298,8 @@ class RQEncoder:
             self._beam_tab, self._beam_tables_key = (cands, seg1, seg2), key
         return self._beam_tab
 
-    def encode_beam(self, x: torch.Tensor, beam: int, chunk_rows: Optional[int] = None,
-                    check: Optional[bool] = None) -> Beam:
-        """Beam-search encode (DESIGN.md §3.1h): ``beam`` partial paths per row, each scored by its original-space
-        reconstruction error, slot 0 always the greedy path (``paths[:, 0] == encode(x)``), the answer the slot with
-        the smallest finite error (lowest slot on ties), so never worse than greedy.  1 <= beam <= ops.TOPK_MAX.
-        Domain: the fused encoders (``self.fused``: one dimension group, no weights, L in {1, 3}) with
-        ``residual_global_id=True``; anything else raises ValueError.  f16 / bf16 rows stay 16-bit.  A row with a
-        non-finite value gets ids -1 and NaN errors; a row without a live path (penalty groups only) raises the
-        KeyError ``encode`` raises.  Rows are processed in chunks of ``chunk_rows`` (default ``2**21 // beam``, so a
-        chunk holds at most 2^21 items and its temporaries, about ``items * (12 * beam + 48)`` bytes, stay under
-        300 MB at beam 8).  ``check`` as in ``encode``."""
-        if check is None:
-            check = not torch.cuda.is_current_stream_capturing()
+    def _beam_input(self, x, beam):
+        """encode_beam's domain and refusals; the rows as the kernels read them and the beam as an int."""
         beam = int(beam)
         if not 1 <= beam <= ops.TOPK_MAX:
             raise ValueError(f"encode_beam: beam = {beam} (1..{ops.TOPK_MAX})")
@@ -319,6 +317,22 @@ class RQEncoder:
             x = x.float()
         x = x.contiguous()
         self.last_row_format = ops.ROW_FORMAT_NAMES[x.dtype]
+        return x, beam
+
+    def encode_beam(self, x: torch.Tensor, beam: int, chunk_rows: Optional[int] = None,
+                    check: Optional[bool] = None) -> Beam:
+        """Beam-search encode (DESIGN.md §3.1h): ``beam`` partial paths per row, each scored by its original-space
+        reconstruction error, slot 0 always the greedy path (``paths[:, 0] == encode(x)``), the answer the slot with
+        the smallest finite error (lowest slot on ties), so never worse than greedy.  1 <= beam <= ops.TOPK_MAX.
+        Domain: the fused encoders (``self.fused``: one dimension group, no weights, L in {1, 3}) with
+        ``residual_global_id=True``; anything else raises ValueError.  f16 / bf16 rows stay 16-bit.  A row with a
+        non-finite value gets ids -1 and NaN errors; a row without a live path (penalty groups only) raises the
+        KeyError ``encode`` raises.  Rows are processed in chunks of ``chunk_rows`` (default ``2**21 // beam``, so a
+        chunk holds at most 2^21 items and its temporaries, about ``items * (12 * beam + 48)`` bytes, stay under
+        300 MB at beam 8).  ``check`` as in ``encode``."""
+        if check is None:
+            check = not torch.cuda.is_current_stream_capturing()
+        x, beam = self._beam_input(x, beam)
         n, dev, B, L = x.shape[0], x.device, beam, self.L
         chunk = int(chunk_rows) if chunk_rows else max(1, (1 << 21) // B)
         chunk = max(1, min(chunk, (2 ** 31 - 1) // B))
@@ -346,9 +360,11 @@ class RQEncoder:
             self.check_errors()
         return Beam(ids, rec, paths, perr, slot)
 
-    def _beam_chunk(self, x, B, paths, perr):
+    def _beam_chunk(self, x, B, paths, perr, depth=None):
         """One chunk of encode_beam: level 0 is rqsid_assign_topk with k = B and a merge with beam_in = 1; the
-        later levels expand the B items of every row under their own parents and merge B * B expansions."""
+        later levels expand the B items of every row under their own parents and merge B * B expansions.
+        ``depth``: stop after level depth - 1 (probe_prefixes); ``paths`` is then [n, B, depth]."""
+        depth = self.L if depth is None else depth
         n, dev = x.shape[0], x.device
         norm = self.sem.normalize_residual
         cands, seg1, seg2 = self._beam_tables(dev)
@@ -356,7 +372,7 @@ class RQEncoder:
         loc, glob, dist = ops.assign_topk(x, self.pcs[0], ops.single_segment(n, dev), self.raw_cands[0], B,
                                           workspace=self._tws, check=False)
         st = ops.beam_merge(n, 1, B, B, 0, loc, glob, dist, use_global=True, dead_key=self.need[0])
-        if self.L == 3:
+        if self.L == 3 and depth >= 2:
             items = n * B
             mult, n_groups = self._last_mult(), self.n_groups
             den1 = torch.empty(items, dtype=torch.float32, device=dev) if norm else None
@@ -365,6 +381,10 @@ class RQEncoder:
             exp = ops.beam_expand(x, B, self.pcs[1], b, cands[1], B, fused=fr, workspace=self._xws, check=False)
             st = ops.beam_merge(n, B, B, B, 1, *exp, scale_in=st.scale, den=den1, path_in=st.path, use_global=False,
                                 key_mult=mult, dead_key=n_groups)
+            if depth == 2:
+                paths.copy_(st.path.view(n, B, 2))
+                perr.copy_(st.rec.view(n, B))
+                return
             if (self.need[0] - 1) * mult + self.need[1] - 1 >= n_groups:  # as _last_level_buckets (one host sync)
                 gmax = int(st.key.max().item())
                 if gmax > n_groups:
@@ -376,8 +396,55 @@ class RQEncoder:
             exp = ops.beam_expand(x, B, self.pcs[2], b, cands[2], B, fused=fr, workspace=self._xws, check=False)
             st = ops.beam_merge(n, B, B, B, 2, *exp, scale_in=st.scale, den=den2, path_in=st.path,
                                 use_global=not self.sem.remap_last)
-        paths.copy_(st.path.view(n, B, self.L))
+        paths.copy_(st.path.view(n, B, depth))
         perr.copy_(st.rec.view(n, B))
+
+    def probe_prefixes(self, q: torch.Tensor, depth: int, probes: int, chunk_rows: Optional[int] = None,
+                       check: Optional[bool] = None) -> torch.Tensor:
+        """The ``probes`` ID prefixes of length ``depth`` nearest to every row of ``q``: i32 [M, probes, depth], the
+        beam of ``encode_beam`` stopped after level ``depth - 1``.  Slot 0 is
+        ``encode(q)[:, :depth]``; the live slots hold pairwise distinct prefixes in ascending (error, parent, place)
+        order after slot 0; a dead slot is -1.  ``probe_prefixes(q, L, B)`` equals ``encode_beam(q, B).paths``.
+        Domain and refusals are ``encode_beam``'s."""
+        if check is None:
+            check = not torch.cuda.is_current_stream_capturing()
+        depth = int(depth)
+        if not 1 <= depth <= self.L:
+            raise ValueError(f"probe_prefixes: depth = {depth} (1..{self.L})")
+        q, B = self._beam_input(q, probes)
+        n, dev = q.shape[0], q.device
+        chunk = int(chunk_rows) if chunk_rows else max(1, (1 << 21) // B)
+        chunk = max(1, min(chunk, (2 ** 31 - 1) // B))
+        paths = torch.empty((n, B, depth), dtype=torch.int32, device=dev)
+        perr = torch.empty((n, B), dtype=torch.float32, device=dev)
+        if n:
+            if self._tws is None:
+                self._tws = ops.TopKWorkspace(min(n, chunk), B, self.device)
+            if self._xws is None:
+                self._xws = ops.BeamWorkspace(min(n, chunk) * B, B, self.device)
+        for r0 in range(0, n, chunk):
+            self._beam_chunk(q[r0:r0 + chunk], B, paths[r0:r0 + chunk], perr[r0:r0 + chunk], depth)
+        if check:
+            self.check_errors()
+        return paths
+
+    def search(self, x: torch.Tensor, index: "ops.IdCells", q: torch.Tensor, k: int = 10, probes: int = 4,
+               depth: Optional[int] = None, metric: str = "cosine",
+               query_self: Optional[torch.Tensor] = None,
+               workspace: Optional["ops.ProbeKnnWorkspace"] = None) -> "IndexSearch":
+        """The k nearest rows of the catalogue ``x`` for every row of ``q``, looked up through the IDs alone
+        (DESIGN.md §3.3f): ``probe_prefixes(q, depth, probes)``, their position ranges in ``index`` (the ``IdCells``
+        of the catalogue's IDs) and one ``ops.probe_knn`` over ``index.order``.  ``depth`` defaults to
+        max(1, L - 1).  ``scanned`` counts the catalogue positions each query read.  ``workspace``: a reusable
+        ``ops.ProbeKnnWorkspace`` (its ``counters()`` then describe this search)."""
+        depth = max(1, self.L - 1) if depth is None else int(depth)
+        prefixes = self.probe_prefixes(q, depth, probes)
+        lo, hi = index.prefix_ranges(prefixes)
+        if q.dtype != x.dtype:
+            q = q.to(x.dtype)
+        rows, val, scanned = ops.probe_knn(x, q.contiguous(), k, lo, hi, metric=metric, order=index.order,
+                                           query_self=query_self, workspace=workspace)
+        return IndexSearch(rows, val, scanned, prefixes)
 
     def _last_level_buckets(self, out, l, n, device):
         if self.sem.match_lookup:

@@ -1004,6 +1004,39 @@ class HierarchicalRQKMeans:
         x, _ = shard_rows(X, self.device, None)
         return neighbor_report(self._encoder(False), x, sample=sample, seed=seed, k=k, metric=metric)
 
+    def index_quality(self, X: np.ndarray, sample: int = 50000, seed: int = 0, k: int = 10, metric: str = "cosine",
+                      probes=(1, 2, 4, 8)) -> Dict:
+        """What a search through the training-consistent IDs of ``X`` finds: recall of the exact ``k`` nearest rows
+        and the share of the catalogue read, per prefix depth and number of probed prefixes (neighbor_report.py's
+        ``index_recall`` has the keys).  Single process only: with a process group it raises."""
+        x = self._single_process_rows("index_quality", X)
+        from .neighbor_report import index_recall
+        return index_recall(self._encoder(False), x, sample=sample, seed=seed, k=k, metric=metric, probes=probes)
+
+    def build_index(self, X: np.ndarray) -> None:
+        """Keep the catalogue ``X`` and the cell index of its training-consistent IDs on the device for ``search``
+        (an index of its own: ``collision_report`` and ``predict_unique`` keep theirs, over their own rows, for
+        ``find_rows_by_prefix``).  Single process only."""
+        x = self._single_process_rows("build_index", X)
+        enc = self._encoder(False)
+        self._search_index = (x, enc.id_index(enc.encode(x)))
+
+    def search(self, Q: np.ndarray, k: int = 10, probes: int = 4, depth: Optional[int] = None,
+               metric: str = "cosine"):
+        """The ``k`` nearest catalogue rows of every row of ``Q`` among the rows under the ``probes`` ID prefixes of
+        length ``depth`` (default max(1, L - 1)) nearest to it: ``RQEncoder.search`` on the catalogue of
+        ``build_index``.  Returns numpy ``(rows int64 [M, k], val float32 [M, k], scanned int64 [M])``; -1 / +inf past
+        the rows those prefixes hold.  Single process only."""
+        if self.group is not None:
+            raise NotImplementedError("search: the multi-GPU form is not built (single process only)")
+        if getattr(self, "_search_index", None) is None:
+            raise RuntimeError("search: call build_index(X) first")
+        x, index = self._search_index
+        q = self._single_process_rows("search", Q).to(x.dtype)
+        out = self._encoder(False).search(x, index, q, k=k, probes=probes, depth=depth, metric=metric)
+        return (out.rows.cpu().numpy().astype(np.int64), out.val.cpu().numpy(),
+                out.scanned.cpu().numpy().astype(np.int64))
+
     def _single_process_rows(self, who: str, X: np.ndarray):
         if not self.is_trained or not self.cluster_centers_list:
             raise RuntimeError("Model not trained. Call train() first or load a trained model.")

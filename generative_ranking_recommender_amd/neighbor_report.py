@@ -12,6 +12,13 @@ to the lowest row number, no distance matrix):
   ``metric``, ``mean_neighbor_value`` (per slot: the mean distance / similarity of the filled slots; None for a slot
   nobody fills), ``counters`` (the kernel's: queries ranked from their lists, (query, chunk) pairs that took the
   all-rows pass, queries without an answer) and ``depths``.
+* ``index_recall``: what a search THROUGH the IDs finds (``RQEncoder.search``: the query's ``P`` nearest ID prefixes of
+  a depth, the rows under them, ``ops.probe_knn``): one exact unrestricted search is the truth, then one probe search
+  per (depth, P).  Per pair, in ``searches``: ``depth``, ``probes``, ``recall`` (the truth's filled slots the search
+  also returned / all filled slots), ``all_found`` (share of the sampled rows with a neighbour whose every true
+  neighbour was returned), ``mean_scanned_share`` (catalogue positions read per query / rows) and ``counters`` (the
+  probe kernel's: queries ranked from their lists, (query, probe) items that took the all-rows pass, queries without
+  an answer, tile visits).  Top level: ``rows``, ``sample``, ``seed``, ``k``, ``metric``.
 * ``neighbors_in_cluster``: ``find_neighbors`` for many rows at once: the ``top_n`` nearest rows among those that share
   the row's first ``depth`` IDs, the row itself excluded.
 
@@ -66,6 +73,55 @@ def neighbor_report(enc, x: torch.Tensor, ids: Optional[torch.Tensor] = None, sa
             "recall": float(shared.sum()) / total if total else None,
             "all_shared": float(((shared == per_query) & (per_query > 0)).sum()) / answered if answered else None,
             "none_shared": float(((shared == 0) & (per_query > 0)).sum()) / answered if answered else None})
+    return report
+
+
+def _found(truth: torch.Tensor, got: torch.Tensor) -> torch.Tensor:
+    """bool [M, k]: the truth's filled slots whose row the search returned as well."""
+    return (truth >= 0) & (truth[:, :, None] == got[:, None, :]).any(-1)
+
+
+def index_recall(enc, x: torch.Tensor, ids: Optional[torch.Tensor] = None, sample: int = 50000, seed: int = 0,
+                 k: int = 10, metric: str = "cosine", depths: Optional[Sequence[int]] = None,
+                 probes: Sequence[int] = (1, 2, 4, 8), comm=None) -> Dict:
+    """``enc``: an ``RQEncoder`` in ``encode_beam``'s domain; ``x``: the catalogue on the device; ``ids``: its IDs
+    (default ``enc.encode(x)``); ``depths``: the prefix depths to probe (default 1 .. L); ``probes``: the numbers of
+    prefixes per query.  The sampled rows are the queries, each excluded from its own answer."""
+    from . import ops
+    if comm is not None:
+        raise NotImplementedError("index_recall: the multi-GPU form is not built (single process only)")
+    n = x.shape[0]
+    if n == 0:
+        raise ValueError("index_recall: no rows")
+    if ids is None:
+        ids = enc.encode(x)
+    L = ids.shape[1]
+    depths = list(range(1, L + 1)) if depths is None else [int(p) for p in depths]
+    if any(not 1 <= p <= L for p in depths):
+        raise ValueError(f"index_recall: depths must lie in 1..{L}")
+    probes = [int(p) for p in probes]
+    rows = sample_rows(n, sample, seed)
+    q_rows = torch.from_numpy(rows).to(x.device)
+    q = x[q_rows].contiguous()
+    q_self = q_rows.to(torch.int32).contiguous()
+    truth, _ = ops.row_knn(x, q, k, metric, query_self=q_self)
+    per_query = (truth >= 0).sum(1)
+    answered = int((per_query > 0).sum())
+    total = int(per_query.sum())
+    index = enc.id_index(ids.to(torch.int32).contiguous())
+    report = {"rows": int(n), "sample": int(len(rows)), "seed": int(seed), "k": int(k), "metric": metric,
+              "searches": []}
+    for depth in depths:
+        for P in probes:
+            ws = ops.ProbeKnnWorkspace(n, len(rows), P, k, x.device)
+            got = enc.search(x, index, q, k=k, probes=P, depth=depth, metric=metric, query_self=q_self, workspace=ws)
+            found = _found(truth, got.rows).sum(1)
+            report["searches"].append({
+                "depth": depth, "probes": P,
+                "recall": float(found.sum()) / total if total else None,
+                "all_found": float(((found == per_query) & (per_query > 0)).sum()) / answered if answered else None,
+                "mean_scanned_share": float(got.scanned.double().mean()) / n,
+                "counters": ws.counters()})
     return report
 
 

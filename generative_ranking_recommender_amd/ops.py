@@ -801,6 +801,75 @@ def row_knn(x: torch.Tensor, q: torch.Tensor, k: int, metric: str = "l2", order:
     return rows, val
 
 
+PROBE_MAX = 32  # RQSID_PROBE_MAX
+PROBE_KNN_WORD = ("bit 1: a row_index or query_self entry outside [0, n_rows) was skipped; bit 4: a probe range end "
+                  "outside [0, n_rows] or lo > hi was clamped (lo > hi: empty); bit 8: two ranges of one query "
+                  "overlapped and the one with the higher probe index was dropped for that query "
+                  "(include/rqsid.h rqsid_probe_knn)")
+
+
+class ProbeKnnWorkspace(_RowPairWorkspace):
+    """Scratch of rqsid_probe_knn: the norm terms of rows and queries, the cleaned ranges, the items' order and one
+    list of k + 8 (value, row) pairs and one record per (query, probe) item; bytes [4, 20) of the header are the
+    call's four counters."""
+
+    def __init__(self, n_rows: int, n_queries: int, n_probes: int, k: int, device):
+        super().__init__("rqsid_probe_knn_workspace_bytes",
+                         lib().rqsid_probe_knn_workspace_bytes(n_rows, n_queries, n_probes, k), device)
+        self.n_rows, self.n_queries, self.n_probes, self.k = n_rows, n_queries, n_probes, k
+
+    def counters(self) -> dict:
+        """Of the last call (one host sync): queries ranked from their lists alone, (query, probe) items that took
+        the all-rows pass, queries without an answer, tile visits of the screen."""
+        c = self.buf[4:20].view(torch.int32).tolist()
+        return {"from_lists": c[0], "all_rows_items": c[1], "non_finite_queries": c[2], "tile_visits": c[3]}
+
+
+def probe_knn(x: torch.Tensor, q: torch.Tensor, k: int, probe_lo: torch.Tensor, probe_hi: torch.Tensor,
+              metric: str = "l2", order: Optional[torch.Tensor] = None, query_self: Optional[torch.Tensor] = None,
+              workspace: Optional[ProbeKnnWorkspace] = None, check: Optional[bool] = None):
+    """The exact k nearest rows of ``x`` for every row of ``q`` among the rows at a few position ranges of ``order``
+    (include/rqsid.h rqsid_probe_knn): the search through an ID index.
+
+    ``x``, ``q``, ``k``, ``metric``, ``order`` (i32 [N], position -> row; None = identity) and ``query_self`` as for
+    ``row_knn``; ``probe_lo`` / ``probe_hi``: i32 [M, P], half-open position ranges (``IdCells.prefix_ranges``, or
+    ``Buckets.seg_row_off`` entries).  Query i searches the union of its ranges.  Returns ``(rows, val, scanned)``:
+    i32 [M, k], f32 [M, k], i32 [M] (the positions in the query's cleaned ranges).  ``check`` (default: on unless the
+    stream is being captured): read the workspace's error word after the call (one host sync) and raise if a table
+    entry was clamped or a range dropped."""
+    if check is None:
+        check = not torch.cuda.is_current_stream_capturing()
+    if metric not in KNN_METRICS:
+        raise ValueError(f"rqsid_probe_knn: metric must be 'l2' or 'cosine', not {metric!r}")
+    if not 1 <= int(k) <= KNN_MAX:
+        raise ValueError(f"rqsid_probe_knn: k must lie in 1..{KNN_MAX}, not {k}")
+    x_format, n, d, m = _row_pair_args("rqsid_probe_knn", x, q, order, None, query_self, None, True)
+    _require_device(probe_lo, probe_hi)
+    if probe_lo.dim() != 2 or probe_lo.shape != probe_hi.shape or probe_lo.shape[0] != m or \
+            probe_lo.dtype != torch.int32 or probe_hi.dtype != torch.int32:
+        raise ValueError("rqsid_probe_knn: probe_lo and probe_hi must be int32 [M, P]")
+    n_probes = probe_lo.shape[1]
+    if not 1 <= n_probes <= PROBE_MAX:
+        raise ValueError(f"rqsid_probe_knn: 1..{PROBE_MAX} probes per query, not {n_probes}")
+    probe_lo, probe_hi = probe_lo.contiguous(), probe_hi.contiguous()
+    dev = x.device
+    rows = torch.empty((m, k), dtype=torch.int32, device=dev)
+    val = torch.empty((m, k), dtype=torch.float32, device=dev)
+    scanned = torch.zeros(m, dtype=torch.int32, device=dev)
+    need = int(lib().rqsid_probe_knn_workspace_bytes(n, m, n_probes, k))
+    if need < 0:
+        _lib.check(need, "rqsid_probe_knn_workspace_bytes")
+    if workspace is None or workspace.bytes < need:
+        workspace = ProbeKnnWorkspace(n, m, n_probes, k, dev)
+    _lib.check(lib().rqsid_probe_knn(_ptr(x), x_format, n, d, _ptr(order), _ptr(q), m, _ptr(query_self), n_probes,
+                                     _ptr(probe_lo), _ptr(probe_hi), KNN_METRICS[metric], int(k), _ptr(rows),
+                                     _ptr(val), _ptr(scanned), _ptr(workspace.buf), workspace.bytes, _stream()),
+               "rqsid_probe_knn")
+    if check:
+        check_error_words([workspace.error_word()], "rqsid_probe_knn", PROBE_KNN_WORD)
+    return rows, val, scanned
+
+
 CELLS_FINE_MAX = 8192        # RQSID_CELLS_FINE_MAX
 CELLS_GROUPS_MAX = 1 << 24   # the wrapper's limit on the product of every level's size but the last
 CELLS_COUNTERS = 37
@@ -897,6 +966,32 @@ class IdCells:
         first, last = torch.searchsorted(keys, bounds).tolist()
         p0, p1 = self.cell_off[torch.tensor([first, last], device=keys.device)].tolist()
         return first, last, (p0 if last > first else p1), p1
+
+    def prefix_ranges(self, prefixes: torch.Tensor):
+        """``prefix_range``'s positions for a batch: ``prefixes`` int [..., p] with 1 <= p <= L gives ``(lo, hi)``,
+        int32 tensors of shape [...] on the index's device, without a host read (beyond ``n_cells``, read once and
+        cached).  A prefix with a negative or out-of-range value gives (0, 0), an absent one lo == hi."""
+        dev = self.cell_off.device
+        prefixes = torch.as_tensor(prefixes, device=dev)
+        L = len(self.sizes)
+        if prefixes.dim() < 1 or not 1 <= prefixes.shape[-1] <= L or prefixes.dtype.is_floating_point:
+            raise ValueError(f"prefixes must be an int tensor [..., p] with 1 <= p <= {L}")
+        p = prefixes.shape[-1]
+        v = prefixes.long()
+        sizes = torch.tensor(self.sizes[:p], dtype=torch.int64, device=dev)
+        bad = ((v < 0) | (v >= sizes)).any(-1)
+        num = torch.zeros(v.shape[:-1], dtype=torch.int64, device=dev)
+        for j in range(p):
+            num = num * self.sizes[j] + v[..., j].clamp(0, self.sizes[j] - 1)
+        below = _prod(self.sizes[p:])
+        keys = self.keys()
+        first = torch.searchsorted(keys, (num * below).reshape(-1)).reshape(num.shape)
+        last = torch.searchsorted(keys, ((num + 1) * below).reshape(-1)).reshape(num.shape)
+        off = self.cell_off.long()
+        p0, p1 = off[first], off[last]
+        lo = torch.where(last > first, p0, p1)
+        zero = torch.zeros_like(lo)
+        return torch.where(bad, zero, lo).to(torch.int32), torch.where(bad, zero, p1).to(torch.int32)
 
     def ids_of(self, cells) -> torch.Tensor:
         """The ID tuples of cell numbers ``cells``: i32 [M, L]."""

@@ -33,7 +33,7 @@ class SemanticIDTrainer:
     def __init__(self, config, use_test_config: bool = False, device=None, group=None,
                  report_quantization: bool = False, report_margins: bool = False, report_beam: int = 0,
                  report_clusters: int = 0, report_neighbors: int = 0, report_collisions: bool = False,
-                 dedup_token: bool = False):
+                 dedup_token: bool = False, report_index: int = 0):
         self.config = config
         # opt-in: also write collision_report.json (HierarchicalRQKMeans.collision_report of the training rows: the
         # figures of the reference's debug_collisions.py and analyze_semantic_ids.py); dedup_token also writes
@@ -52,6 +52,13 @@ class SemanticIDTrainer:
         if group is not None and self.report_neighbors:
             raise NotImplementedError("SemanticIDTrainer: report_neighbors is single-process only (the multi-GPU "
                                       "neighbour report is not built)")
+        # opt-in (a sample size): also write index_recall_report.json (HierarchicalRQKMeans.index_quality of the
+        # training rows: what a search through the IDs finds of a row's exact nearest rows, per depth and number of
+        # probed prefixes).  Single process only: refused here, before any training
+        self.report_index = int(report_index or 0)
+        if group is not None and self.report_index:
+            raise NotImplementedError("SemanticIDTrainer: report_index is single-process only (the multi-GPU index "
+                                      "search is not built)")
         # opt-in (a sample size, the reference's is 50000): also write cluster_quality_report.json
         # (HierarchicalRQKMeans.cluster_quality of the training rows: the three scores of the reference's
         # calculate_metrics.py per prefix depth).  Single process only: refused here, before any training
@@ -137,6 +144,10 @@ class SemanticIDTrainer:
             neighbors = model.neighbor_quality(vectors, sample=self.report_neighbors)
             rq_io.write_json(str(self.output_dir / "neighbor_report.json"), neighbors)
             result["neighbor_report"] = neighbors
+        if self.report_index:
+            index = model.index_quality(vectors, sample=self.report_index)
+            rq_io.write_json(str(self.output_dir / "index_recall_report.json"), index)
+            result["index_recall_report"] = index
         if self.report_collisions:
             collisions = model.collision_report(vectors)
             rq_io.write_json(str(self.output_dir / "collision_report.json"), collisions)

@@ -420,6 +420,41 @@ int rqsid_row_knn(const void* x, int32_t x_format, int64_t n_rows, int32_t dim,
                   int32_t* out_row, float* out_val,
                   void* workspace, int64_t workspace_bytes, void* stream);
 
+/* The exact k nearest rows of every query among the rows of a few position ranges of the order: the search through
+ * the ID index.  x, x_format, row_index (position -> row, NULL = identity), q, query_self, metric and
+ * k mean what they mean for rqsid_row_knn.  probe_lo / probe_hi are [n_queries][n_probes] half-open position ranges
+ * (the cell index's order with its cell_off, or any rqsid_bucket output, serves as it is).  Query i searches the
+ * UNION of its ranges; the result is the exact k nearest rows of that set with rqsid_row_knn's fp64 key, arithmetic,
+ * tie rule (lowest row number of x), self exclusion by index, -1 / +inf past the eligible rows, and its rules for
+ * rows and queries without a key.  With one range equal to a segment the outputs are byte-identical to rqsid_row_knn
+ * with that query_seg, with [0, n_rows) to the unrestricted call.  The outputs are a function of the row SET: the
+ * order of a query's probes, the order of the queries, a permutation of row_index inside ranges and added empty
+ * ranges change no output byte.  out_scanned (may be NULL): per query the number of positions in its cleaned ranges.
+ * Method: (query, probe) items, read in place, are ordered by the start of their range (rqsid_bucket's kernels; the
+ * order decides only which items share a block); a block of up to 128 consecutive items merges their tile intervals into
+ * runs and sweeps run after run with rqsid_row_knn's fp32 MFMA screen, each item limited to its range, keeping the
+ * k + 8 smallest screen values per item; one fold per query over its items' lists, then the fp64 pass over what can
+ * still place and over every row of an item whose list could not be proven complete.
+ * Limits: 1 <= n_probes <= RQSID_PROBE_MAX; n_queries * n_probes < 2^31; the rest as rqsid_row_knn.  n_queries == 0
+ * or n_rows == 0 succeeds without touching anything.  RQSID_E_ARG / RQSID_E_WORKSPACE before any HIP call.
+ * Stream-ordered, no host synchronisation, graph-capturable; no float atomics; two calls on the same inputs give
+ * identical output bytes.
+ * Workspace (rqsid_probe_knn_workspace_bytes): bytes [0, 4) the sticky error word, zeroed by the caller once, never
+ * by a call: 1 = a row_index / query_self entry outside the rows (skipped / taken as -1); 4 = a range end outside
+ * [0, n_rows] or lo > hi (clamped; lo > hi is empty); 8 = two ranges of one query overlap (the one with the higher
+ * probe index is dropped whole for that query).  Bytes [4, 20): four int32 counters zeroed by every call: queries
+ * ranked from their lists alone, (query, probe) items that took the all-rows pass, queries without an answer, tile
+ * visits of the screen. */
+#define RQSID_PROBE_MAX 32
+int64_t rqsid_probe_knn_workspace_bytes(int64_t n_rows, int32_t n_queries, int32_t n_probes, int32_t k);
+int rqsid_probe_knn(const void* x, int32_t x_format, int64_t n_rows, int32_t dim,
+                    const int32_t* row_index,
+                    const void* q, int32_t n_queries, const int32_t* query_self,
+                    int32_t n_probes, const int32_t* probe_lo, const int32_t* probe_hi,
+                    int32_t metric, int32_t k,
+                    int32_t* out_row, float* out_val, int32_t* out_scanned,
+                    void* workspace, int64_t workspace_bytes, void* stream);
+
 /* The ID cell index: which rows share a full ID, each row's place among them, and the collision
  * counters: the base of the reference's debug_collisions.py / analyze_semantic_ids.py figures, of
  * evaluate_semantic_ids.py's find_songs_by_semantic_id and of a disambiguating last token.
