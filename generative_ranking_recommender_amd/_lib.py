@@ -23,7 +23,7 @@ SRCS = [PKG / "csrc" / "rqsid.hip", PKG / "csrc" / "assign.hip", PKG / "csrc" / 
         PKG / "csrc" / "auction.hip",
         PKG / "csrc" / "auction_seg.hip", PKG / "csrc" / "quant_error.hip", PKG / "csrc" / "assign_topk.hip",
         PKG / "csrc" / "beam.hip", PKG / "csrc" / "silhouette.hip", PKG / "csrc" / "row_knn.hip",
-        PKG / "csrc" / "id_cells.hip", PKG / "csrc" / "probe_knn.hip"]
+        PKG / "csrc" / "id_cells.hip", PKG / "csrc" / "probe_knn.hip", PKG / "csrc" / "id_trie.hip"]
 DEPS = SRCS + [PKG / "csrc" / "internal.h", PKG / "csrc" / "assign_common.h", PKG / "csrc" / "assign_plan.h",
                PKG / "csrc" / "topk_kernel.h", PKG / "csrc" / "exact_row.h", PKG / "csrc" / "tile_rows.h",
                PKG / "csrc" / "knn_core.h"]
@@ -101,6 +101,13 @@ SIGNATURES = {
     "rqsid_id_cells_workspace_bytes": (c_i64, [c_i64, c_i32, c_i32]),
     "rqsid_id_cells": (c_i32, [c_i64, c_vp, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                c_vp, c_vp, c_i64, c_vp]),
+    "rqsid_id_trie_workspace_bytes": (c_i64, [c_i64, c_i32]),
+    "rqsid_id_trie": (c_i32, [c_i64, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "rqsid_trie_mask_workspace_bytes": (c_i64, [c_i64]),
+    "rqsid_trie_mask": (c_i32, [c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_i32, c_i64,
+                                c_vp, c_i32, c_i32, c_i64, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "rqsid_trie_beam_step": (c_i32, [c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_i32, c_i32, c_vp, c_vp,
+                                     c_vp, c_i32, c_i32, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "rqsid_scale_groups": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp]),
     "rqsid_centroid_tile_rows": (c_i32, []),
     "rqsid_centroid_accumulate": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_i64, c_vp, c_vp]),

@@ -686,6 +686,14 @@ class RQEncoder:
             raise ValueError(f"ids must be [N, {self.L}], got {tuple(ids.shape)}")
         return ops.id_cells(ids, self.id_sizes(), rank_key)
 
+    def id_trie(self, ids: torch.Tensor, tokens: Optional["ops.TokenMap"] = None, comm=None):
+        """The ``SemanticIDTrie`` of ``ids`` [N, L] (semantic_id_trie.py): the trie a constrained decoder walks, over
+        this encoder's level sizes; ``tokens`` None: the identity token map.  Single process only."""
+        if comm is not None:
+            raise NotImplementedError("id_trie: the multi-GPU form is not built (single process only)")
+        from .semantic_id_trie import SemanticIDTrie
+        return SemanticIDTrie.from_index(self.id_index(ids), tokens)
+
     def unique_ids(self, x: torch.Tensor, ids: Optional[torch.Tensor] = None) -> torch.Tensor:
         """int32 [N, L + 1]: the semantic IDs of ``x`` (default ``encode(x)``) with one more token that makes every row
         distinct: the row's rank among the rows that share its ID, by original-space reconstruction error

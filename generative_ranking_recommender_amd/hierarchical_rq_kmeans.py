@@ -1057,6 +1057,19 @@ class HierarchicalRQKMeans:
         out, self._id_index = collision_report(self._encoder(False), x, top=top, members=members, return_index=True)
         return out
 
+    def build_trie(self, X: np.ndarray, tokenizer=None):
+        """The ``SemanticIDTrie`` (semantic_id_trie.py) of the training-consistent IDs of ``X``: what a generative
+        retriever's constrained decoding walks.  ``tokenizer``: an object of the reference's tokenizer shape
+        (``ops.TokenMap.from_tokenizer``); None: the identity token map.  Single process only."""
+        x = self._single_process_rows("build_trie", X)
+        enc = self._encoder(False)
+        tokens = None
+        if tokenizer is not None:
+            from . import ops
+            tokens = ops.TokenMap.from_tokenizer(tokenizer, getattr(tokenizer, "eos_token_id", None) or 0,
+                                                 levels=len(self.config.layer_clusters), device=self.device)
+        return enc.id_trie(enc.encode(x), tokens)
+
     def predict_unique(self, X: np.ndarray, ids: Optional[np.ndarray] = None) -> np.ndarray:
         """int64 [N, L + 1]: ``predict(X, reference_quirks=False)`` (or the training-consistent ``ids`` [N, L] the
         caller already holds) with one more token that makes every row's ID distinct, the row's rank by

@@ -98,6 +98,23 @@ def write_semantic_ids(path: str, semantic_ids: Dict[str, List[int]]) -> int:
     return len(unique)
 
 
+def read_semantic_ids(path: str, levels: int = 3):
+    """``(song_ids, int32 [N, levels])`` of a ``song_semantic_ids.jsonl``; an entry whose ``semantic_ids`` does not
+    hold ``levels`` values is skipped, as the reference's SemanticIDTrie skips it (semantic_id_trie.py:61-63)."""
+    song_ids, rows = [], []
+    with open(path, "r", encoding="utf-8") as f:
+        for line in f:
+            if not line.strip():
+                continue
+            item = json.loads(line)
+            ids = item["semantic_ids"]
+            if len(ids) != levels:
+                continue
+            song_ids.append(item.get("song_id"))
+            rows.append([int(v) for v in ids])
+    return song_ids, np.asarray(rows, dtype=np.int32).reshape(-1, levels)
+
+
 def semantic_id_statistics(semantic_ids: Dict[str, List[int]], need_clusters: Sequence[int]) -> Dict:
     """train_semantic_ids.py:266-310 _generate_statistics."""
     stats = {"total_songs": len(semantic_ids),

@@ -7,6 +7,7 @@ There is deliberately no CPU implementation: a CPU tensor or a missing
 """
 from __future__ import annotations
 
+import copy
 import ctypes
 from dataclasses import dataclass
 from typing import Optional, Sequence
@@ -1071,6 +1072,332 @@ def id_cells(ids: torch.Tensor, sizes: Optional[Sequence[int]] = None, rank_key:
     out.counters = workspace.counters().clone()  # the workspace may serve another call
     if check:
         check_error_words([buckets.error_word(), workspace.error_word()], "rqsid_id_cells", ID_CELLS_WORD)
+    return out
+
+
+TRIE_LEVELS_MAX = 8       # RQSID_TRIE_LEVELS_MAX
+TRIE_VOCAB_MAX = 1 << 20  # RQSID_TRIE_VOCAB_MAX
+TRIE_BEAM_MAX = 64        # RQSID_TRIE_BEAM_MAX
+IDS_FORMATS = {torch.int32: 0, torch.int64: 1}  # RQSID_IDS_*
+ID_TRIE_WORD = "bit 1: a cell outside sizes, or not above the cell before it, was dropped"
+TRIE_MASK_WORD = ("bit 1: a child range outside the counts was clamped; bit 2: a level_tok entry outside [-1, vocab) "
+                  "was skipped")
+TRIE_KIND_WALK, TRIE_KIND_COMPLETE, TRIE_KIND_DEAD = 0, 1, 2
+
+
+def _sizes_array(sizes):
+    return (ctypes.c_int32 * len(sizes))(*sizes)
+
+
+@dataclass
+class IdTrie:
+    """The trie tables of ``id_trie`` (device tensors; include/rqsid.h rqsid_id_trie): ``count`` i32 [L + 1],
+    ``value`` i32 [L, capacity], ``child_off`` i32 [L, capacity + 1], ``leaf_cell`` i32 [capacity]; entries past the
+    counts are not written.  ``sizes``: the levels' sizes."""
+    count: torch.Tensor
+    value: torch.Tensor
+    child_off: torch.Tensor
+    leaf_cell: torch.Tensor
+    sizes: tuple
+    _counts: Optional[tuple] = None
+    error: Optional[torch.Tensor] = None  # i32 [1]: the build's error word (a copy)
+
+    @property
+    def levels(self) -> int:
+        return len(self.sizes)
+
+    @property
+    def capacity(self) -> int:
+        return int(self.leaf_cell.numel())
+
+    def counts(self) -> tuple:
+        """Nodes per depth 0 .. L (one host read, then cached)."""
+        if self._counts is None:
+            self._counts = tuple(int(v) for v in self.count.tolist())
+        return self._counts
+
+    def _table_args(self):
+        return (self.capacity, self.levels, _sizes_array(self.sizes), _ptr(self.count), _ptr(self.value),
+                _ptr(self.child_off))
+
+    def to_arrays(self) -> dict:
+        """The written part of the tables as numpy arrays (for ``numpy.savez``)."""
+        import numpy as np
+        cnt = self.counts()
+        out = {"sizes": np.asarray(self.sizes, dtype=np.int32), "count": np.asarray(cnt, dtype=np.int32),
+               "leaf_cell": self.leaf_cell[:cnt[-1]].cpu().numpy()}
+        for d in range(self.levels):
+            out[f"value{d}"] = self.value[d, :cnt[d + 1]].cpu().numpy()
+            out[f"child_off{d}"] = self.child_off[d, :cnt[d] + 1].cpu().numpy()
+        return out
+
+    @classmethod
+    def from_arrays(cls, arrays, device) -> "IdTrie":
+        sizes = tuple(int(s) for s in arrays["sizes"])
+        cnt = [int(c) for c in arrays["count"]]
+        L, cap = len(sizes), cnt[-1]
+        value = torch.zeros(L, cap, dtype=torch.int32, device=device)
+        child_off = torch.zeros(L, cap + 1, dtype=torch.int32, device=device)
+        for d in range(L):
+            value[d, :cnt[d + 1]] = torch.as_tensor(arrays[f"value{d}"], dtype=torch.int32).to(device)
+            child_off[d, :cnt[d] + 1] = torch.as_tensor(arrays[f"child_off{d}"], dtype=torch.int32).to(device)
+        return cls(torch.tensor(cnt, dtype=torch.int32, device=device), value, child_off,
+                   torch.as_tensor(arrays["leaf_cell"], dtype=torch.int32).to(device).contiguous(), sizes, tuple(cnt))
+
+
+def id_trie_tables(cell_group: torch.Tensor, cell_fine: torch.Tensor, sizes: Sequence[int],
+                   keep: Optional[torch.Tensor] = None, check: bool = True) -> IdTrie:
+    """rqsid_id_trie on bare cell arrays (i32 [n_cells] each, as rqsid_id_cells writes them)."""
+    _require_device(cell_group, cell_fine, keep)
+    sizes = tuple(int(s) for s in sizes)
+    n = int(cell_group.numel())
+    if cell_group.dtype != torch.int32 or cell_fine.dtype != torch.int32 or cell_fine.numel() != n:
+        raise ValueError("rqsid_id_trie: cell_group and cell_fine must be int32 [n_cells]")
+    if keep is not None:
+        if keep.numel() != n or keep.dtype not in (torch.uint8, torch.bool):
+            raise ValueError("rqsid_id_trie: keep must be uint8 or bool [n_cells]")
+        keep = keep.to(torch.uint8)
+    dev = cell_group.device
+    L = len(sizes)
+    nbytes = int(lib().rqsid_id_trie_workspace_bytes(n, L))
+    if nbytes < 0:
+        _lib.check(nbytes, "rqsid_id_trie_workspace_bytes")
+    ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=dev)
+    ws[:256].zero_()
+    rows = max(L, 0)
+    trie = IdTrie(torch.zeros(rows + 1, dtype=torch.int32, device=dev),
+                  torch.empty(rows, n, dtype=torch.int32, device=dev),
+                  (torch.empty if n else torch.zeros)(rows, n + 1, dtype=torch.int32, device=dev),
+                  torch.empty(n, dtype=torch.int32, device=dev), sizes)
+    if n == 0:
+        trie.count[0] = 1  # (the entry touches nothing without cells: count = {1, 0, ...}, child_off = 0)
+    _lib.check(lib().rqsid_id_trie(n, _ptr(cell_group), _ptr(cell_fine), L, _sizes_array(sizes), _ptr(keep),
+                                   _ptr(trie.count), _ptr(trie.value), _ptr(trie.child_off), _ptr(trie.leaf_cell),
+                                   _ptr(ws), nbytes, _stream()), "rqsid_id_trie")
+    trie.error = ws[:4].view(torch.int32).clone()
+    if check:
+        check_error_words([ws[:4].view(torch.int32)], "rqsid_id_trie", ID_TRIE_WORD)
+    return trie
+
+
+def id_trie(index: IdCells, keep: Optional[torch.Tensor] = None, check: bool = True) -> IdTrie:
+    """The trie of a cell index (include/rqsid.h rqsid_id_trie).  ``keep``: uint8 / bool [n_cells] (None: every cell); a
+    cell with ``keep == 0`` is left out, as the reference leaves out a sequence with an unknown token
+    (``TokenMap.keep_cells``).  ``leaf_cell`` numbers the index's cells, so ``index.cell_off[trie.leaf_cell[j]]`` is where
+    leaf j's rows start in ``index.order``.  ``check``: read the error word (one host sync) and raise if it is set."""
+    n = index.n_cells
+    return id_trie_tables(index.cell_group[:n].contiguous(), index.cell_fine[:n].contiguous(), index.sizes, keep, check)
+
+
+class TokenMap:
+    """The tokenizer as two tables of token numbers, on the device: ``tok_code`` i32 [vocab_size] (-1 for a token that
+    is no ID token, else ``level << 24 | value``) and ``level_tok`` i32 [sum(sizes)] (the levels one after another: the
+    token number of (level, value), or -1).  ``level_tokens``: per level, the token number of each value (-1: none).
+    Raises ValueError if two (level, value) pairs share a token number or a token number is outside the vocabulary."""
+
+    def __init__(self, vocab_size: int, level_tokens, eos_token_id: int, device=None):
+        import numpy as np
+        self.vocab_size = int(vocab_size)
+        self.eos_token_id = int(eos_token_id)
+        levels = [np.asarray(t, dtype=np.int64).reshape(-1) for t in level_tokens]
+        self.sizes = tuple(len(t) for t in levels)
+        if not 1 <= len(levels) <= TRIE_LEVELS_MAX or any(s < 1 for s in self.sizes):
+            raise ValueError(f"TokenMap: 1 .. {TRIE_LEVELS_MAX} non-empty levels are needed, got sizes {self.sizes}")
+        if not 1 <= self.vocab_size <= TRIE_VOCAB_MAX:
+            raise ValueError(f"TokenMap: vocab_size = {self.vocab_size} outside [1, {TRIE_VOCAB_MAX}]")
+        if not 0 <= self.eos_token_id < self.vocab_size:
+            raise ValueError(f"TokenMap: eos_token_id = {self.eos_token_id} outside the vocabulary")
+        if any(s > 1 << 24 for s in self.sizes):
+            raise ValueError("TokenMap: a level holds more than 2^24 values")
+        code = np.full(self.vocab_size, -1, dtype=np.int32)
+        for l, toks in enumerate(levels):
+            if ((toks < -1) | (toks >= self.vocab_size)).any():
+                bad = int(toks[(toks < -1) | (toks >= self.vocab_size)][0])
+                raise ValueError(f"TokenMap: token number {bad} of level {l} is outside the vocabulary "
+                                 f"[0, {self.vocab_size})")
+            have = np.nonzero(toks >= 0)[0]
+            t = toks[have]
+            if len(np.unique(t)) != len(t) or (code[t] != -1).any():
+                raise ValueError(f"TokenMap: a token number of level {l} names more than one (level, value) pair")
+            code[t] = (l << 24) | have.astype(np.int32)
+        self.level_tok_host = np.concatenate(levels).astype(np.int32)
+        self.tok_code_host = code
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
+        self.tok_code = torch.from_numpy(code).to(dev)
+        self.level_tok = torch.from_numpy(self.level_tok_host).to(dev)
+        self.level_off = tuple(int(v) for v in np.concatenate([[0], np.cumsum(self.sizes)]))
+
+    @classmethod
+    def identity(cls, sizes, device=None) -> "TokenMap":
+        """token = the level's offset + value, eos = sum(sizes), vocab_size = sum(sizes) + 1."""
+        sizes = [int(s) for s in sizes]
+        offs = [sum(sizes[:l]) for l in range(len(sizes))]
+        return cls(sum(sizes) + 1, [range(o, o + s) for o, s in zip(offs, sizes)], sum(sizes), device)
+
+    @classmethod
+    def from_tokenizer(cls, tokenizer, eos_token_id: int, levels: int = 3, device=None) -> "TokenMap":
+        """From an object shaped like the reference's tokenizer: ``tokenizer.base_tokenizer.convert_tokens_to_ids`` and
+        ``.unk_token_id``, ``tokenizer.layer_vocab_sizes['l1' ...]``, tokens named ``<id_l{n}_{v}>``.  An unknown token
+        at level >= 1 becomes -1 (the cells that use it are dropped through ``keep_cells``, as the reference drops
+        them).  An unknown level-0 token raises ValueError: the reference would then take the unknown-token number
+        itself for a level-1 token and start a prefix at every unknown token of the input; that is refused here."""
+        base = tokenizer.base_tokenizer
+        unk = base.unk_token_id
+        tables = []
+        for l in range(levels):
+            n = int(tokenizer.layer_vocab_sizes[f"l{l + 1}"])
+            toks = [base.convert_tokens_to_ids(f"<id_l{l + 1}_{v}>") for v in range(n)]
+            if l == 0 and any(t == unk or t is None for t in toks):
+                v = [t == unk or t is None for t in toks].index(True)
+                raise ValueError(f"TokenMap.from_tokenizer: <id_l1_{v}> is unknown to the tokenizer; the reference "
+                                 "would treat the unknown-token number as a level-1 token, which is refused here")
+            tables.append([-1 if (t == unk or t is None) else int(t) for t in toks])
+        vocab = getattr(tokenizer, "vocab_size", None)
+        if vocab is None:
+            vocab = len(base)
+        return cls(int(vocab), tables, eos_token_id, device)
+
+    def with_eos(self, eos_token_id: int) -> "TokenMap":
+        """The same tables (shared, not copied) with another eos."""
+        if not 0 <= int(eos_token_id) < self.vocab_size:
+            raise ValueError(f"TokenMap: eos_token_id = {eos_token_id} outside the vocabulary")
+        other = copy.copy(self)
+        other.eos_token_id = int(eos_token_id)
+        return other
+
+    def with_vocab(self, vocab_size: int) -> "TokenMap":
+        """The same (level, value) -> token table for scores of another width (a model's logits may be padded beyond
+        the tokenizer's vocabulary); raises ValueError if a token number or eos does not fit."""
+        offs = self.level_off
+        return TokenMap(vocab_size, [self.level_tok_host[offs[l]:offs[l + 1]] for l in range(len(self.sizes))],
+                        self.eos_token_id, self.level_tok.device)
+
+    def keep_cells(self, index: IdCells) -> torch.Tensor:
+        """uint8 [n_cells]: 1 for a cell whose every level value has a token."""
+        n = index.n_cells
+        ids = index.ids_of(torch.arange(n, device=self.level_tok.device)).long()
+        keep = torch.ones(n, dtype=torch.bool, device=self.level_tok.device)
+        for l in range(len(self.sizes)):
+            keep &= self.level_tok[self.level_off[l] + ids[:, l]] >= 0
+        return keep.to(torch.uint8)
+
+
+class TrieMaskWorkspace:
+    """Scratch of rqsid_trie_mask: 16 bytes per row behind a 256-byte header zeroed here once: bytes [0, 4) the sticky
+    error word, bytes [4, 16) the call's counters (rows of kind 0 / 1 / 2)."""
+
+    def __init__(self, n_rows: int, device):
+        self.bytes = int(lib().rqsid_trie_mask_workspace_bytes(n_rows))
+        if self.bytes < 0:
+            _lib.check(self.bytes, "rqsid_trie_mask_workspace_bytes")
+        self.buf = torch.empty(self.bytes, dtype=torch.uint8, device=device)
+        self.buf[:256].zero_()
+
+    def error_word(self) -> torch.Tensor:
+        return self.buf[:4].view(torch.int32)
+
+    def counters(self) -> torch.Tensor:
+        return self.buf[4:16].view(torch.int32)
+
+
+@dataclass
+class TrieMaskRows:
+    """Per row of ``trie_mask``: ``kind`` (0 walked, 1 complete, 2 dead), ``node`` (the node reached, -1 unless kind 0),
+    ``count`` (allowed tokens); ``kinds``: i32 [3], the rows of each kind."""
+    kind: torch.Tensor
+    node: torch.Tensor
+    count: torch.Tensor
+    kinds: torch.Tensor
+
+
+def _check_tokens(who: str, trie: IdTrie, tokens: TokenMap) -> None:
+    if tuple(tokens.sizes) != tuple(trie.sizes):
+        raise ValueError(f"{who}: the token map's sizes {tokens.sizes} are not the trie's {trie.sizes}")
+
+
+def trie_mask(trie: IdTrie, tokens: TokenMap, input_ids: torch.Tensor, scores: torch.Tensor,
+              workspace: Optional[TrieMaskWorkspace] = None, check: bool = True) -> TrieMaskRows:
+    """Constrained-decoding mask in place (include/rqsid.h rqsid_trie_mask): ``scores`` [B, V] (f32 / f16 / bf16, unit
+    stride inside a row, any row stride >= V) keeps the entries of the tokens the trie allows after each row of
+    ``input_ids`` [B, T] (int32 / int64) and gets -inf everywhere else.  One launch sequence, no host read (``check``:
+    read the error word afterwards, one host sync, and raise if it is set)."""
+    who = "rqsid_trie_mask"
+    _check_tokens(who, trie, tokens)
+    for t in (input_ids, scores):
+        if t.device.type != "cuda":
+            raise RuntimeError("rqsid kernels run on the GPU only: got a %s tensor" % t.device.type)
+    if scores.dim() != 2 or scores.dtype not in ROW_FORMATS:
+        raise ValueError(f"{who}: scores must be float32 / float16 / bfloat16 [B, V]")
+    B, V = scores.shape
+    if input_ids.dim() != 2 or input_ids.shape[0] != B or input_ids.dtype not in IDS_FORMATS:
+        raise ValueError(f"{who}: input_ids must be int32 / int64 [B, T] with the scores' B")
+    if V != tokens.vocab_size:
+        raise ValueError(f"{who}: scores hold {V} tokens a row, the token map {tokens.vocab_size}")
+    T = input_ids.shape[1]
+    if T and B and input_ids.stride(1) != 1:
+        input_ids = input_ids.contiguous()
+    if B and V and (scores.stride(1) != 1 or (B > 1 and scores.stride(0) < V)):
+        raise ValueError(f"{who}: scores need unit stride inside a row and a row stride >= V")
+    dev = scores.device
+    if workspace is None or workspace.bytes < 256 + 16 * B:
+        workspace = TrieMaskWorkspace(B, dev)
+    out = TrieMaskRows(*(torch.empty(B, dtype=torch.int32, device=dev) for _ in range(3)), workspace.counters())
+    ld = scores.stride(0) if B > 1 else max(V, 1)
+    ids_ld = input_ids.stride(0) if (B > 1 and T) else max(T, 1)
+    _lib.check(lib().rqsid_trie_mask(*trie._table_args(), _ptr(input_ids) if T and B else None,
+                                     IDS_FORMATS[input_ids.dtype], B, T, ids_ld, _ptr(scores),
+                                     ROW_FORMATS[scores.dtype], V, ld, _ptr(tokens.tok_code), _ptr(tokens.level_tok),
+                                     tokens.eos_token_id, _ptr(out.kind), _ptr(out.node), _ptr(out.count),
+                                     _ptr(workspace.buf), workspace.bytes, _stream()), who)
+    out.kinds = workspace.counters().clone() if B and V else torch.zeros(3, dtype=torch.int32, device=dev)
+    if check:
+        check_error_words([workspace.error_word()], who, TRIE_MASK_WORD)
+    return out
+
+
+@dataclass
+class TrieBeamStep:
+    """``trie_beam_step``'s slots, [B, beam_out] each: ``node`` (depth d + 1), ``score`` f32, ``parent`` (the hypothesis
+    it extends), ``value`` (its level-d ID value), ``token``; an unfilled slot holds -1 / -inf / -1 / -1 / -1."""
+    node: torch.Tensor
+    score: torch.Tensor
+    parent: torch.Tensor
+    value: torch.Tensor
+    token: torch.Tensor
+
+
+def trie_beam_step(trie: IdTrie, tokens: TokenMap, depth: int, node_in: torch.Tensor,
+                   score_in: Optional[torch.Tensor], logp: torch.Tensor, beam_out: int) -> TrieBeamStep:
+    """One constrained beam step over trie nodes (include/rqsid.h rqsid_trie_beam_step): ``node_in`` i32 [B, beam_in]
+    depth-``depth`` nodes, ``score_in`` f32 [B, beam_in] or None, ``logp`` [B * beam_in, V] (f32 / f16 / bf16, unit
+    stride inside a row); the best ``beam_out`` children by (score descending, hypothesis, value)."""
+    who = "rqsid_trie_beam_step"
+    _check_tokens(who, trie, tokens)
+    _require_device(node_in, score_in)
+    if logp.device.type != "cuda":
+        raise RuntimeError("rqsid kernels run on the GPU only: got a %s tensor" % logp.device.type)
+    if node_in.dim() != 2 or node_in.dtype != torch.int32:
+        raise ValueError(f"{who}: node_in must be int32 [B, beam_in]")
+    B, beam_in = node_in.shape
+    if score_in is not None and (score_in.dtype != torch.float32 or tuple(score_in.shape) != (B, beam_in)):
+        raise ValueError(f"{who}: score_in must be float32 [B, beam_in]")
+    if logp.dim() != 2 or logp.dtype not in ROW_FORMATS or logp.shape[0] != B * beam_in:
+        raise ValueError(f"{who}: logp must be float32 / float16 / bfloat16 [B * beam_in, V]")
+    V = logp.shape[1]
+    if V != tokens.vocab_size:
+        raise ValueError(f"{who}: logp holds {V} tokens a row, the token map {tokens.vocab_size}")
+    if logp.shape[0] and (logp.stride(1) != 1 or (logp.shape[0] > 1 and logp.stride(0) < V)):
+        raise ValueError(f"{who}: logp needs unit stride inside a row and a row stride >= V")
+    ld = logp.stride(0) if logp.shape[0] > 1 else V
+    dev = node_in.device
+    n_out = max(int(beam_out), 0)
+    out = TrieBeamStep(torch.empty(B, n_out, dtype=torch.int32, device=dev),
+                       torch.empty(B, n_out, dtype=torch.float32, device=dev),
+                       *(torch.empty(B, n_out, dtype=torch.int32, device=dev) for _ in range(3)))
+    _lib.check(lib().rqsid_trie_beam_step(*trie._table_args(), int(depth), B, beam_in, int(beam_out), _ptr(node_in),
+                                          _ptr(score_in), _ptr(logp), ROW_FORMATS[logp.dtype], V, ld,
+                                          _ptr(tokens.level_tok), _ptr(out.node), _ptr(out.score), _ptr(out.parent),
+                                          _ptr(out.value), _ptr(out.token), _stream()), who)
     return out
 
 

@@ -33,8 +33,14 @@ class SemanticIDTrainer:
     def __init__(self, config, use_test_config: bool = False, device=None, group=None,
                  report_quantization: bool = False, report_margins: bool = False, report_beam: int = 0,
                  report_clusters: int = 0, report_neighbors: int = 0, report_collisions: bool = False,
-                 dedup_token: bool = False, report_index: int = 0):
+                 dedup_token: bool = False, report_index: int = 0, report_trie: bool = False):
         self.config = config
+        # opt-in: also write trie_report.json (SemanticIDTrie.report of the training rows' IDs: the reference's
+        # get_statistics, the nodes per depth and the fan-out per depth).  Single process only: refused here
+        self.report_trie = bool(report_trie)
+        if group is not None and self.report_trie:
+            raise NotImplementedError("SemanticIDTrainer: report_trie is single-process only (the multi-GPU cell "
+                                      "index is not built)")
         # opt-in: also write collision_report.json (HierarchicalRQKMeans.collision_report of the training rows: the
         # figures of the reference's debug_collisions.py and analyze_semantic_ids.py); dedup_token also writes
         # song_semantic_ids_unique.jsonl, the training-consistent IDs with one more token (the row's rank among the
@@ -152,6 +158,10 @@ class SemanticIDTrainer:
             collisions = model.collision_report(vectors)
             rq_io.write_json(str(self.output_dir / "collision_report.json"), collisions)
             result["collision_report"] = collisions
+        if self.report_trie:
+            trie = model.build_trie(vectors).report()
+            rq_io.write_json(str(self.output_dir / "trie_report.json"), trie)
+            result["trie_report"] = trie
         if self.dedup_token:
             # the trained IDs themselves (the tuples of song_semantic_ids.jsonl), each with its rank as one more token
             trained = np.stack([np.asarray(t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else t)

@@ -505,6 +505,106 @@ int rqsid_id_cells(int64_t n_rows, const int32_t* row_index, int32_t n_groups, c
                    int32_t* cell_off, int32_t* cell_group, int32_t* cell_fine,
                    void* workspace, int64_t workspace_bytes, void* stream);
 
+/* The ID trie: the tables a generative retriever's constrained decoding walks, built from the cells
+ * of rqsid_id_cells: the device form of the reference's SemanticIDTrie (src/generator/semantic_id_trie.py).
+ * cell_group[n_cells] / cell_fine[n_cells] as rqsid_id_cells writes them (distinct, lexicographically ascending);
+ * sizes[levels] (HOST array, required even without cells) the levels' sizes: the last level is the fine ID (at most
+ * RQSID_CELLS_FINE_MAX), the group the mixed-radix number of the others (product at most 2^24); with one level, level
+ * 0 is the group and the fine ID is 0.  keep[n_cells] (uint8, NULL = all): a cell with keep == 0 is not in the trie
+ * (the reference never inserts a sequence with an unknown token).
+ * A node of depth d (1 .. levels) is a distinct d-prefix among the kept cells, numbered from 0 in lexicographic order
+ * per depth; the depth-levels nodes are the kept cells in order; the root is the one node of depth 0.
+ * Outputs (int32, device; entries past the counts are not written):
+ *   count[levels + 1]                 count[0] = 1, count[d] the nodes of depth d
+ *   value[levels][n_cells]            value[d - 1][j] the level-(d - 1) ID value of depth-d node j
+ *   child_off[levels][n_cells + 1]    child_off[d][j] the first depth-(d + 1) child of depth-d node j, and
+ *                                     child_off[d][count[d]] = count[d + 1]; the children of a node ascend in value
+ *   leaf_cell[n_cells]                the cell number of depth-levels node j (cell_off[leaf_cell[j]]: its rows)
+ * Workspace (rqsid_id_trie_workspace_bytes): bytes [0, 4) the sticky error word, zeroed by the caller once: 1 = a cell
+ * outside sizes, or not above the cell before it (cell i is compared with cell i - 1 as given); the cell is dropped.
+ * The tables are nested and in bounds whatever the input, and are the kept cells' trie whenever those ascend.
+ * Limits: n_cells < 2^31, 1 <= levels <= RQSID_TRIE_LEVELS_MAX; n_cells == 0 succeeds without touching anything (the
+ * caller then holds count = {1, 0, ...} and child_off[d][0] = 0 itself).  RQSID_E_ARG / RQSID_E_WORKSPACE before any
+ * HIP call.  Stream-ordered, no host synchronisation (the counts stay on the device; every grid is sized by n_cells),
+ * graph-capturable.  Integer arithmetic only, no atomics but the error word's OR; no write position comes from an
+ * input: each is a scan of flags, compared with the capacity.  Two calls give identical bytes.
+ * Method: flag the cells, scan, compact the kept cells' IDs; flag per kept cell and depth "starts a node" (one bit per
+ * depth in a byte), scan all depths at once, emit.  A scan is per-tile sums (2048 cells a block), one block over the
+ * tile sums (a run of tiles per thread) and the consuming pass: 8 launches for any n_cells. */
+#define RQSID_TRIE_LEVELS_MAX 8
+int64_t rqsid_id_trie_workspace_bytes(int64_t n_cells, int32_t levels);
+int rqsid_id_trie(int64_t n_cells, const int32_t* cell_group, const int32_t* cell_fine, int32_t levels,
+                  const int32_t* sizes, const uint8_t* keep,
+                  int32_t* count, int32_t* value, int32_t* child_off, int32_t* leaf_cell,
+                  void* workspace, int64_t workspace_bytes, void* stream);
+
+/* Constrained-decoding mask: the reference's ConstrainedLogitsProcessor.__call__ (_extract_current_prefix,
+ * get_valid_next_tokens, masked_fill; src/generator/semantic_id_trie.py) for a whole batch in one call.
+ * The trie: capacity (the n_cells the tables were built with: value is [levels][capacity], child_off [levels]
+ * [capacity + 1]), levels, sizes (host), count, value, child_off.  input_ids [n_rows][n_tokens] with row stride ids_ld,
+ * int32 (RQSID_IDS_I32) or int64 (RQSID_IDS_I64); n_tokens may be 0 (input_ids then NULL).  scores [n_rows][vocab]
+ * with row stride ld >= vocab in elements, x_format RQSID_X_F32 / F16 / BF16, masked in place; the pointer and the
+ * rows need only the element's alignment.  The token table: tok_code[vocab] = -1 for a token that is no ID token, else
+ * level << 24 | value; level_tok[sum(sizes)], the levels one after another: the token number of (level, value) or -1;
+ * eos in [0, vocab).  vocab <= RQSID_TRIE_VOCAB_MAX.
+ * Per row: (1) the last position whose token has level 0 in tok_code starts the prefix (a token number outside
+ * [0, vocab) is no ID token); without one the prefix is empty, else it is the tokens from there on, at most `levels`.
+ * (2) a prefix of `levels` tokens (kind 1, complete): every level-0 token (level_tok[v] >= 0 for v < sizes[0], in the
+ * trie or not) and eos are allowed.  (3) otherwise (kind 0) the trie is walked from the root: the token at place t
+ * must have level t and its value be a child of the current node (binary search in the node's child range); the
+ * tokens of the reached node's children are allowed.  (4) a failed walk or an empty allowed set (kind 2, dead): only
+ * eos.  (5) scores[b][v] keeps its bytes for an allowed v (NaN included) and becomes -inf of the format for every other
+ * v < vocab (NaN included); elements in [vocab, ld) are not touched.
+ * Optional outputs per row (NULL: not wanted): out_kind, out_node (the node reached, -1 unless kind 0), out_count (the
+ * allowed tokens; exact when level_tok names each token once and agrees with tok_code).
+ * Workspace (rqsid_trie_mask_workspace_bytes): bytes [0, 4) the sticky error word, zeroed by the caller once: 1 = a
+ * child range outside the counts (clamped), 2 = a level_tok entry outside [-1, vocab) (skipped).  Bytes [4, 16): three
+ * int32 counters zeroed by every call: the rows of kind 0, 1, 2.
+ * n_rows == 0 or vocab == 0 succeeds without touching anything.  RQSID_E_ARG / RQSID_E_WORKSPACE before any HIP call
+ * (n_rows x ceil(vocab / 8192) must stay below 2^31).  Stream-ordered, no host read, graph-capturable; no float
+ * atomics; no address is formed from an unchecked token number, child offset, value or level_tok entry; two calls on
+ * the same inputs leave identical bytes.
+ * Method: a walk kernel (one wave per row) writes each row's kind, prefix length and child range to the workspace; the
+ * mask kernel (one block per 8192-element slice of a row) sets the allowed tokens of its slice in an LDS bitmap and
+ * stores 16-byte pieces: a piece without an allowed token is stored without being read, one with only allowed tokens
+ * is left alone, a mixed one is read, blended and stored; the row's unaligned head and tail go element by element. */
+#define RQSID_TRIE_VOCAB_MAX 1048576
+#define RQSID_IDS_I32 0
+#define RQSID_IDS_I64 1
+int64_t rqsid_trie_mask_workspace_bytes(int64_t n_rows);
+int rqsid_trie_mask(int64_t capacity, int32_t levels, const int32_t* sizes, const int32_t* count,
+                    const int32_t* value, const int32_t* child_off,
+                    const void* input_ids, int32_t ids_format, int64_t n_rows, int32_t n_tokens, int64_t ids_ld,
+                    void* scores, int32_t x_format, int32_t vocab, int64_t ld,
+                    const int32_t* tok_code, const int32_t* level_tok, int32_t eos,
+                    int32_t* out_kind, int32_t* out_node, int32_t* out_count,
+                    void* workspace, int64_t workspace_bytes, void* stream);
+
+/* One constrained beam step over trie nodes (no reference counterpart: the retrieval-style decode of the same trie,
+ * carrying node numbers in place of token rows).  depth d in [0, levels); node_in [n_rows][beam_in] depth-d node
+ * numbers (beam_in = 1 and node 0 at depth 0; a value outside [0, count[d]) is a dead hypothesis); score_in
+ * [n_rows][beam_in] fp32 (NULL = 0); logp [n_rows * beam_in][ld] in x_format, ld >= vocab; level_tok as above.
+ * A candidate is (h, c): a hypothesis h that is not dead and whose score_in is no NaN, and a child c of its node whose
+ * token t = level_tok[d][value[c]] lies in [0, vocab).  Its score is s = fl32(score_in[h] + (float) logp[b beam_in +
+ * h][t]); it is live unless s is NaN or -inf.  The output holds the first beam_out live candidates in the order (s
+ * descending, h ascending, value ascending; -0 equals +0): node_out (depth d + 1), score_out, and, where wanted (NULL:
+ * not), parent_out (h), value_out, token_out; unfilled slots hold -1 / -inf / -1 / -1 / -1.
+ * beam_in, beam_out in 1 .. RQSID_TRIE_BEAM_MAX; a node's first 2^24 children are candidates.  n_rows == 0 succeeds
+ * without touching anything; RQSID_E_ARG before any HIP call.  Stream-ordered, no workspace, no atomics, no write
+ * position from a device counter; a pure function of its inputs, bit-reproducible.
+ * Method: one block per batch row; every candidate has its own 64-bit key (the score's place in order above the
+ * inverted (h, child rank)), each thread holds the largest key of its own candidates, and a round takes the block's
+ * largest, after which only the thread that owned it looks through its candidates again.  64 x 8192 candidates per
+ * row work, slowly (2048 candidates per thread and round for the owning thread). */
+#define RQSID_TRIE_BEAM_MAX 64
+int rqsid_trie_beam_step(int64_t capacity, int32_t levels, const int32_t* sizes, const int32_t* count,
+                         const int32_t* value, const int32_t* child_off,
+                         int32_t depth, int64_t n_rows, int32_t beam_in, int32_t beam_out,
+                         const int32_t* node_in, const float* score_in,
+                         const void* logp, int32_t x_format, int32_t vocab, int64_t ld, const int32_t* level_tok,
+                         int32_t* node_out, float* score_out, int32_t* parent_out, int32_t* value_out,
+                         int32_t* token_out, void* stream);
+
 /* y = x * w_g per dimension group (hierarchical_rq_kmeans.py:583-604). */
 int rqsid_scale_groups(const float* x, int64_t n, int32_t dim, const int32_t* group_dims,
                        int32_t n_groups, const float* weights, float* out, void* stream);
