@@ -1,6 +1,6 @@
 """Plain numpy / dict model of the ID trie, of rqsid_trie_mask's rules 1 - 5 and of rqsid_trie_beam_step's order
 (include/rqsid.h), written from those rules: the yardstick of the trie tests, checked itself against the reference's
-recorded outputs (tests/golden/trie.npz) in test_trie_model.py."""
+recorded outputs (tests/golden/trie.npz, trie_long.npz) in test_trie_model.py."""
 import numpy as np
 
 KIND_WALK, KIND_COMPLETE, KIND_DEAD = 0, 1, 2
@@ -31,6 +31,31 @@ def tables(cells, levels, keep=None):
         prev = uniq
     return dict(count=np.asarray(count, dtype=np.int32), value=value, child_off=child_off,
                 leaf_cell=idx.astype(np.int32))
+
+
+def tables_sorted(cells, levels, keep=None):
+    """``tables`` for millions of cells, from the order alone: a kept cell starts a depth-d node where its d-prefix
+    differs from the kept cell before it (an OR along the levels of the element-wise comparison), a node's number is
+    the count of such heads before it (``cumsum``), and a node's first child is where its number first appears among
+    the parents of the depth below (``searchsorted``).  Checked against ``tables`` in test_trie_model.py."""
+    cells = np.asarray(cells, dtype=np.int64).reshape(-1, levels)
+    idx = np.arange(len(cells))
+    if keep is not None:
+        idx = idx[np.asarray(keep).astype(bool)]
+    kept = cells[idx]
+    head = np.ones((len(kept), levels), dtype=bool)
+    if len(kept) > 1:
+        head[1:] = np.logical_or.accumulate(kept[1:] != kept[:-1], axis=1)
+    count, value, child_off = [1], [], []
+    above = np.zeros(len(kept), dtype=np.int64)  # each kept cell's node number at the depth above
+    for d in range(1, levels + 1):
+        h = head[:, d - 1]
+        child_off.append(np.searchsorted(above[h], np.arange(count[-1] + 1)).astype(np.int32))
+        value.append(kept[h, d - 1].astype(np.int32))
+        count.append(int(h.sum()))
+        above = np.cumsum(h) - 1
+    return dict(count=np.asarray(count, dtype=np.int32), value=value, child_off=child_off,
+                leaf_cell=idx[head[:, levels - 1]].astype(np.int32))
 
 
 class TrieModel:
@@ -118,6 +143,40 @@ class TrieModel:
         out = []
         for _, h, v, s, tok in cands[:beam_out]:
             out.append((self.node_no[depth + 1][prefixes[node_in[h]] + (v,)], s, h, v, tok))
+        while len(out) < beam_out:
+            out.append((-1, np.float32(-np.inf), -1, -1, -1))
+        return out
+
+
+    def candidates(self, depth, node_in, score_in, logp):
+        """Every live candidate of one batch row as arrays (s f32, h, value, token, score_in[h], logp[h, token]), one
+        numpy expression per hypothesis: the same rule as ``beam_step``, for nodes of thousands of children."""
+        prefixes = sorted(self.nodes[depth])
+        cols = [[] for _ in range(6)]
+        for h, n in enumerate(node_in):
+            s_in = np.float32(score_in[h])
+            if not 0 <= n < len(prefixes) or np.isnan(s_in):
+                continue
+            vals = np.asarray(sorted(self.children.get(prefixes[n], ())), dtype=np.int64)
+            toks = self.level_tok[depth][vals]
+            vals = vals[(toks >= 0) & (toks < self.V)]
+            toks = self.level_tok[depth][vals]
+            lp = np.asarray(logp[h], dtype=np.float32)[toks]
+            with np.errstate(invalid="ignore"):
+                s = (s_in + lp).astype(np.float32)
+            live = ~np.isnan(s) & (s != -np.inf)
+            for c, a in zip(cols, (s, np.full(len(s), h), vals, toks, np.full(len(s), s_in, np.float32), lp)):
+                c.append(a[live])
+        kinds = (np.float32, np.int64, np.int64, np.int64, np.float32, np.float32)
+        return tuple(np.concatenate(c).astype(k) if c else np.zeros(0, k) for c, k in zip(cols, kinds))
+
+    def beam_step_wide(self, depth, node_in, score_in, logp, beam_out):
+        """``beam_step`` by one ``lexsort`` of ``candidates`` (checked against ``beam_step`` in test_trie_model.py)."""
+        s, h, v, tok, _, _ = self.candidates(depth, node_in, score_in, logp)
+        order = np.lexsort((v, h, -s))[:beam_out]  # -0.0 == 0.0 for lexsort as well
+        prefixes = sorted(self.nodes[depth])
+        out = [(self.node_no[depth + 1][prefixes[node_in[h[i]]] + (int(v[i]),)], s[i], int(h[i]), int(v[i]),
+                int(tok[i])) for i in order]
         while len(out) < beam_out:
             out.append((-1, np.float32(-np.inf), -1, -1, -1))
         return out

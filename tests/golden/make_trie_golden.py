@@ -1,12 +1,19 @@
-"""Record tests/golden/trie.npz by running the REFERENCE's src/generator/semantic_id_trie.py on the CPU::
+"""Record tests/golden/trie.npz and tests/golden/trie_long.npz by running the REFERENCE's
+src/generator/semantic_id_trie.py on the CPU::
 
-    python tests/golden/make_trie_golden.py <path of the reference checkout>
+    python tests/golden/make_trie_golden.py <path of the reference checkout> trie|long
+
+``trie`` rewrites trie.npz, ``long`` trie_long.npz; each recording leaves the other file alone (an .npz holds the time
+it was written, so a rewrite is never byte-identical).
 
 The module is loaded by path (it imports json / logging / typing / collections, and torch inside __call__) with a
 fake tokenizer object of the shape it reads.  The fixture holds data only: the inputs (the jsonl's entries, the token
 table, token sequences, scores) and the reference's own outputs (masked scores in fp32 / fp16 / bf16,
-get_valid_next_tokens of every prefix of length 0 .. 2, is_valid_sequence samples, get_statistics).  Nothing in the
-package or the tests imports this file.
+get_valid_next_tokens of every prefix of length 0 .. 2, is_valid_sequence samples, get_statistics).  trie_long.npz
+holds rows of 130 tokens over the same IDs and token table (tests/_trie_cases.long_rows: the last level-0 token at
+chosen places up to the row's start, decoys before it), a seed of its own, and per row what the reference's processor
+derived (the length of its prefix, the tokens it allowed) beside the masked scores.  Nothing in the package or the
+tests imports this file.
 """
 import importlib.util
 import itertools
@@ -43,7 +50,8 @@ class _Tokenizer:
         self.layer_vocab_sizes = {f"l{l + 1}": s for l, s in enumerate(SIZES)}
 
 
-def main(reference: Path):
+def setup(reference: Path):
+    """The reference's trie and processor over the fixture's IDs and token table (the same for both recordings)."""
     spec = importlib.util.spec_from_file_location("ref_semantic_id_trie",
                                                   reference / "src" / "generator" / "semantic_id_trie.py")
     ref = importlib.util.module_from_spec(spec)
@@ -74,6 +82,56 @@ def main(reference: Path):
                 f.write(json.dumps({"song_id": f"s{n}", "semantic_ids": e}) + "\n")
         trie = ref.SemanticIDTrie(tokenizer, str(path))
     proc = ref.ConstrainedLogitsProcessor(trie, tokenizer, EOS)
+    return rng, level_tok, ids, entries, trie, proc
+
+
+def masked(proc, input_ids, scores):
+    out = {}
+    for name, dt in (("f32", torch.float32), ("f16", torch.float16), ("bf16", torch.bfloat16)):
+        got = proc(input_ids, scores.to(dt).clone())
+        out[f"masked_{name}"] = got.view(torch.int32 if dt == torch.float32 else torch.int16).numpy()
+    return out
+
+
+def record_long(reference: Path):
+    sys.path.insert(0, str(HERE.parent.parent))
+    from tests import _trie_cases as C
+    _, level_tok, _, _, trie, proc = setup(reference)
+    T, seed = 130, 20261022
+    kept = sorted(trie.valid_semantic_ids)
+    rows, where = C.long_rows(level_tok, VOCAB, kept, T, seed, fill=[0, 3, 4, 5, 6, 7])
+    # what the reference's processor derives for each row, by its own methods
+    prefix_len, kind, allowed = [], [], np.zeros((len(rows), VOCAB), dtype=np.uint8)
+    for b, row in enumerate(rows.tolist()):
+        prefix = proc._extract_current_prefix(row)
+        valid = trie.get_valid_next_tokens(prefix)
+        if len(prefix) == 3:
+            valid, k = set(proc.l1_token_ids) | {EOS}, 1
+        elif valid:
+            k = 0
+        else:
+            valid, k = {EOS}, 2
+        prefix_len.append(len(prefix))
+        kind.append(k)
+        allowed[b, sorted(valid)] = 1
+    rng = np.random.default_rng(seed + 1)
+    scores = torch.from_numpy(rng.standard_normal((len(rows), VOCAB)).astype(np.float32) * 3)
+    scores[:, ::7] = float("nan")
+    scores[5, 9] = float("inf")
+    input_ids = torch.from_numpy(rows)
+    out = masked(proc, input_ids, scores)
+    keep = torch.from_numpy(allowed.astype(bool))
+    assert torch.equal(out["masked_f32"] == torch.tensor(float("-inf")).view(torch.int32), ~keep | (scores == -np.inf))
+    np.savez_compressed(
+        HERE / "trie_long.npz", input_ids=rows.astype(np.int16), where=where.astype(np.int32),
+        prefix_len=np.asarray(prefix_len, dtype=np.int32), kind=np.asarray(kind, dtype=np.int32), allowed=allowed,
+        scores=scores.numpy().view(np.int32), **out)
+    print("wrote", HERE / "trie_long.npz", (HERE / "trie_long.npz").stat().st_size, "bytes;", len(rows), "rows of", T,
+          "tokens; kinds", np.bincount(kind).tolist())
+
+
+def record_trie(reference: Path):
+    rng, level_tok, ids, entries, trie, proc = setup(reference)
 
     def tok(l, v):
         return int(level_tok[l][v])
@@ -121,10 +179,7 @@ def main(reference: Path):
     scores[:, ::5] = float("nan")
     scores[2, :] = float("nan")
     scores[4, 7] = float("inf")
-    out = {}
-    for name, dt in (("f32", torch.float32), ("f16", torch.float16), ("bf16", torch.bfloat16)):
-        got = proc(input_ids, scores.to(dt).clone())
-        out[f"masked_{name}"] = got.view(torch.int32 if dt == torch.float32 else torch.int16).numpy()
+    out = masked(proc, input_ids, scores)
     stats = trie.get_statistics()
 
     def dist(d):
@@ -147,6 +202,6 @@ def main(reference: Path):
 
 
 if __name__ == "__main__":
-    if len(sys.argv) != 2:
+    if len(sys.argv) != 3 or sys.argv[2] not in ("trie", "long"):
         sys.exit(__doc__)
-    main(Path(sys.argv[1]))
+    (record_trie if sys.argv[2] == "trie" else record_long)(Path(sys.argv[1]))

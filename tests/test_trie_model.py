@@ -8,6 +8,7 @@ import torch
 
 from generative_ranking_recommender_amd import io as rq_io
 from generative_ranking_recommender_amd import ops
+from tests import _trie_cases as C
 from tests import _trie_model as M
 
 
@@ -84,6 +85,152 @@ def test_beam_order_of_the_model():
     logp[0, 2], logp[0, 3] = -np.inf, np.nan
     out = m.beam_step(1, [0, 1], np.zeros(2, np.float32), logp, 2)
     assert [(o[0], o[2], o[3]) for o in out] == [(2, 1, 0), (-1, -1, -1)]
+
+
+# ------------------------------------------------------------------------- the long recording, tables_sorted
+def test_long_rows_equal_the_references_kinds_and_allowed_sets(golden, g, model):
+    """Rows of 130 tokens: the reference scans the whole row backwards for the last level-1 token."""
+    lg = golden("trie_long")
+    rows = lg["input_ids"].astype(np.int64)
+    assert rows.shape[1] == 130
+    kind, _, count, allowed = model.rows(rows)
+    assert kind.tolist() == lg["kind"].tolist() and set(kind.tolist()) == {0, 1, 2}
+    assert np.array_equal(allowed, lg["allowed"].astype(bool)) and (count == allowed.sum(1)).all()
+    want_len = [0 if w < 0 else min(130 - w, 3) for w in lg["where"]]
+    assert lg["prefix_len"].tolist() == want_len  # the reference found the token the rows were built around
+    C.check_long_rows(model, rows, lg["where"], 130)
+    for name, dtype in (("f32", torch.float32), ("f16", torch.float16), ("bf16", torch.bfloat16)):
+        scores = torch.from_numpy(lg["scores"].view(np.float32)).to(dtype)
+        got = torch.where(torch.from_numpy(allowed), scores, torch.full_like(scores, float("-inf")))
+        bits = torch.int32 if dtype == torch.float32 else torch.int16
+        assert torch.equal(got.view(bits), torch.from_numpy(lg[f"masked_{name}"]))
+
+
+def assert_same_tables(a, b):
+    assert a["count"].tolist() == b["count"].tolist() and a["count"].dtype == b["count"].dtype
+    for key in ("value", "child_off"):
+        assert len(a[key]) == len(b[key])
+        for x, y in zip(a[key], b[key]):
+            assert x.dtype == y.dtype and np.array_equal(x, y)
+    assert a["leaf_cell"].dtype == b["leaf_cell"].dtype and np.array_equal(a["leaf_cell"], b["leaf_cell"])
+
+
+@pytest.mark.parametrize("sizes, rows", [((5, 4, 7), 60), ((50,), 40), ((3, 4, 2, 6), 90), ((2, 2, 2, 2, 2, 2, 2, 2), 200),
+                                         ((128, 128, 256), 3000), ((6, 5, 9), 500), ((5, 4, 7), 1)])
+def test_tables_sorted_equals_tables(sizes, rows):
+    """Every small configuration of test_gpu_id_trie.py, with and without keep (all, some, one subtree, none)."""
+    rng = np.random.default_rng(len(sizes) * 1000 + rows)
+    cells = np.unique(np.stack([rng.integers(0, s, rows) for s in sizes], 1), axis=0)
+    L = len(sizes)
+    assert_same_tables(M.tables_sorted(cells, L), M.tables(cells, L))
+    for keep in (np.random.default_rng(3).random(len(cells)) < 0.6, cells[:, 0] != cells[len(cells) // 2, 0],
+                 ~(cells[:, :2] == cells[min(3, len(cells) - 1), :2]).all(1), np.zeros(len(cells), dtype=bool)):
+        assert_same_tables(M.tables_sorted(cells, L, keep), M.tables(cells, L, keep))
+    empty = np.zeros((0, L), dtype=np.int64)
+    assert_same_tables(M.tables_sorted(empty, L), M.tables(empty, L))
+
+
+@pytest.mark.parametrize("n", C.BUILD_N[:3])
+def test_sampled_cells_of_the_build_tests(n):
+    cells = C.sampled_cells(n)
+    assert len(cells) == n and (np.diff(np.ravel_multi_index(cells.T, C.BUILD_SIZES)) > 0).all()
+    C.check_build_cells(cells, M.tables_sorted(cells, 4))
+    for which in C.BUILD_KEEPS:
+        keep = C.build_keep(cells, which)
+        assert_same_tables(M.tables_sorted(cells, 4, keep), M.tables(cells, 4, keep))
+    assert not C.build_keep(cells, "tile0")[:2048].any()
+
+
+def test_sampled_cells_beyond_one_run_of_tiles():
+    n = C.BUILD_N[-1]
+    cells = C.sampled_cells(n)
+    assert -(-n // 2048) > 1024 and len(cells) == n
+    assert (np.diff(np.ravel_multi_index(cells.T, C.BUILD_SIZES)) > 0).all()
+    C.check_build_cells(cells, M.tables_sorted(cells, 4))
+    keep = C.build_keep(cells, "multiple")
+    assert keep.sum() == 2048 * 1027
+
+
+# ---------------------------------------------------------------------------- the generated inputs of the GPU tests
+@pytest.mark.parametrize("T", C.LONG_T)
+def test_long_rows_hold_what_they_are_meant_to(T):
+    case = C.Case(**C.spec("edge"))
+    rows, where = C.long_rows(case.level_tok, case.V, case.kept, T, seed=T, fill=C.long_fill(case))
+    assert rows.shape[1] == T
+    C.check_long_rows(case.model, rows, where, T)
+    assert ((rows < 0) | (rows >= case.V)).any()
+
+
+@pytest.mark.parametrize("name", ["levels1", "levels4", "levels8", "eos_level0", "eos_level1"])
+def test_rows_of_the_level_and_eos_setups(name):
+    case = C.Case(**C.spec(name))
+    L = len(case.sizes)
+    rows = case.rows_of_every_kind(T=max(L + 2, 5), seed=3, n_random=6)
+    kind, _, count, allowed = case.model.rows(rows)
+    if L == 1:
+        assert set(kind.tolist()) == {0, 1}  # a row is dead only if the root has no child with a token
+        assert case.model.children[()] and all(case.tok(0, v) >= 0 for v in case.model.children[()])
+    else:
+        assert set(kind.tolist()) == {0, 1, 2}
+        assert any((t < 0).any() for t in case.level_tok[1:]) or name.startswith("eos")
+    toks = np.concatenate(case.level_tok)
+    assert (np.diff(toks[toks >= 0]) < 0).any() and (np.diff(toks[toks >= 0]) > 0).any()  # in no monotone order
+    level0 = {int(t) for t in case.level_tok[0]}
+    if name == "eos_level0":  # the complete rows allow the level-0 tokens, eos among them: not one more
+        assert case.eos in level0 and (count[kind == 1] == len(level0)).all()
+    if name == "eos_level1":  # eos among the children of a walked node; dead rows allow exactly it
+        walked = [b for b in range(len(rows)) if kind[b] == 0 and allowed[b, case.eos]]
+        assert walked and (allowed[kind == 2].sum(1) == 1).all() and allowed[kind == 2][:, case.eos].all()
+        assert (count[kind == 1] == len(level0) + 1).all()
+
+
+@pytest.mark.parametrize("name", sorted(C.SPECS))
+def test_every_setup_has_a_valid_token_table(name):
+    spec = C.spec(name)
+    tm = ops.TokenMap(spec["vocab"], spec["level_tok"], spec["eos"], device="cpu")
+    assert tm.sizes == tuple(spec["sizes"])
+
+
+def test_beam_step_wide_equals_beam_step():
+    for name in ("levels1", "levels4", "levels8", "poison"):
+        case = C.Case(**C.spec(name))
+        for depth in range(len(case.sizes)):
+            for fmt in C.FORMATS:
+                n_nodes, beam_in = len(case.model.nodes[depth]), 1 if depth == 0 else 12
+                rng = np.random.default_rng(depth)
+                node_in = rng.integers(0, n_nodes, (2, beam_in)).astype(np.int32)
+                score_in, logp = C.edge_scores(2, beam_in, case.V, fmt, seed=depth)
+                C.dead_hypotheses(node_in, score_in, n_nodes)
+                for b in range(2):
+                    args = (depth, node_in[b].tolist(), score_in[b], logp[b * beam_in:(b + 1) * beam_in], 9)
+                    a, w = case.model.beam_step(*args), case.model.beam_step_wide(*args)
+                    assert [(x[0], np.float32(x[1]).view(np.int32), *x[2:]) for x in a] == [
+                        (x[0], np.float32(x[1]).view(np.int32), *x[2:]) for x in w]
+
+
+@pytest.mark.parametrize("fmt", C.FORMATS)
+def test_edge_scores_tie_only_where_planned(fmt):
+    """The beam tests' scores: exact in the format, subnormals kept by the conversion, no unplanned tie in any row."""
+    dtype = {"f32": torch.float32, "f16": torch.float16, "bf16": torch.bfloat16}[fmt]
+    for name, depth, live in (("poison", 0, 1.0), ("poison", 1, 1.0), ("poison", 2, 1.0), ("fan8192", 1, 0.002)):
+        case = C.Case(**C.spec(name))
+        n_nodes, beam_in, B = len(case.model.nodes[depth]), 64, 3
+        node_in = np.random.default_rng(depth).integers(0, n_nodes, (B, beam_in)).astype(np.int32)
+        score_in, logp = C.edge_scores(B, beam_in, case.V, fmt, seed=depth + 10, live=live)
+        t = torch.from_numpy(logp)
+        back = t.to(dtype).float()  # (a NaN may come back with another payload)
+        assert torch.equal(back.isnan(), t.isnan()) and torch.equal(back.nan_to_num(7.0).view(torch.int32),
+                                                                    t.nan_to_num(7.0).view(torch.int32))
+        tiny = np.abs(logp[np.isfinite(logp) & (logp != 0)]).min()
+        assert tiny < (2.0 ** -14 if fmt == "f16" else 2.0 ** -126)  # subnormal log-probabilities of the format
+        assert (np.abs(score_in[np.isfinite(score_in) & (score_in != 0)]) < 2.0 ** -126).any()  # fp32 denormals
+        assert np.isposinf(score_in).any() and np.isneginf(score_in).any() and (score_in > 0).any()
+        for b in range(B):
+            n, distinct = C.check_ties_are_planned(case.model, depth, node_in[b].tolist(), score_in[b],
+                                                   logp[b * beam_in:(b + 1) * beam_in])
+            assert n > 0 and distinct > 1
+            s = case.model.candidates(depth, node_in[b].tolist(), score_in[b], logp[b * beam_in:(b + 1) * beam_in])[0]
+            assert (s > 0).any() and (s < 0).any() and (b != 0 or np.isposinf(s).any())  # both branches of the order
 
 
 # ------------------------------------------------------------------------------------------------- TokenMap, io
