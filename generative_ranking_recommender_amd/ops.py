@@ -35,6 +35,14 @@ def _require_device(*ts: Optional[torch.Tensor]) -> None:
             raise ValueError("rqsid kernels need contiguous tensors")
 
 
+def _require_f32(who: str, *ts: Optional[torch.Tensor]) -> None:
+    """The kernels behind these wrappers read their rows as fp32 through a raw pointer: any other dtype would be
+    read (and, for an output, written) past its end.  A host-side check of metadata: no device sync."""
+    for t in ts:
+        if t is not None and t.dtype != torch.float32:
+            raise TypeError("%s: rows must be float32, got %s (convert with .float() at the caller)" % (who, t.dtype))
+
+
 def lib():
     return _lib.load()
 
@@ -174,7 +182,7 @@ def match_to_candidates(match: torch.Tensor) -> Candidates:
     _lib.check(lib().rqsid_match_to_candidates(_ptr(match), g, nc, _ptr(base), _ptr(cnt), _ptr(idx), _ptr(flags),
                                                _ptr(ws), wsb, _stream()), "rqsid_match_to_candidates")
     # the maximum allowed count decides the kernel variant; match rows are host-known data
-    cmax = int(match.sum(1).max().item()) if g else 0
+    cmax = int((match != 0).sum(1).max().item()) if g else 0
     return Candidates(base, cnt, cmax, idx, flags)
 
 
@@ -570,20 +578,32 @@ def with_dead_segment(cand: Candidates) -> Candidates:
     return Candidates(torch.cat([cand.base, z]), torch.cat([cand.count, z]), cand.count_max, cand.idx, flags, cand.lid)
 
 
-def _groups_tensor(group_dims: Sequence[int], device) -> torch.Tensor:
-    return torch.tensor(list(group_dims), dtype=torch.int32, device=device)
+MAX_GROUPS = 16  # kMaxGroups (csrc/rqsid.hip)
+
+
+def _groups_tensor(group_dims: Sequence[int], device, dim: Optional[int] = None, who: str = "") -> torch.Tensor:
+    """The dimension groups as a device tensor.  With ``dim``: the widths must be positive, at most MAX_GROUPS and
+    sum to dim (the kernels give whatever lies past the listed widths to the last group)."""
+    gd = [int(g) for g in group_dims]
+    if dim is not None:
+        if not 1 <= len(gd) <= MAX_GROUPS:
+            raise ValueError("%s: %d dimension groups (1 .. %d are supported)" % (who, len(gd), MAX_GROUPS))
+        if min(gd) <= 0 or sum(gd) != dim:
+            raise ValueError("%s: group_dims %s do not split the %d dimensions" % (who, gd, dim))
+    return torch.tensor(gd, dtype=torch.int32, device=device)
 
 
 def residual(x: torch.Tensor, centers: torch.Tensor, ids: torch.Tensor, group_dims: Sequence[int] = (),
              normalize: bool = True, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    _require_f32("residual", x, out)
     ids = ids.to(torch.int32).contiguous()
     centers = centers.float().contiguous()
-    _require_device(x, centers, ids)
+    _require_device(x, centers, ids, out)
     n, d = x.shape
     if out is None:
         out = torch.empty_like(x)
     gd = list(group_dims) or [d]
-    g = _groups_tensor(gd, x.device)
+    g = _groups_tensor(gd, x.device, d if normalize else None, "residual")
     _lib.check(lib().rqsid_residual(_ptr(x), n, d, _ptr(centers), centers.shape[0], _ptr(ids), _ptr(g), len(gd), int(normalize),
                                     _ptr(out), _stream()), "rqsid_residual")
     return out
@@ -1402,10 +1422,13 @@ def trie_beam_step(trie: IdTrie, tokens: TokenMap, depth: int, node_in: torch.Te
 
 
 def scale_groups(x: torch.Tensor, group_dims: Sequence[int], weights: Sequence[float]) -> torch.Tensor:
+    _require_f32("scale_groups", x)
     _require_device(x)
     n, d = x.shape
+    g = _groups_tensor(group_dims, x.device, d, "scale_groups")
+    if len(weights) != len(group_dims):
+        raise ValueError("scale_groups: %d weights for %d dimension groups" % (len(weights), len(group_dims)))
     out = torch.empty_like(x)
-    g = _groups_tensor(group_dims, x.device)
     w = torch.tensor(list(weights), dtype=torch.float32, device=x.device)
     _lib.check(lib().rqsid_scale_groups(_ptr(x), n, d, _ptr(g), len(group_dims), _ptr(w), _ptr(out), _stream()),
                "rqsid_scale_groups")
@@ -1414,7 +1437,9 @@ def scale_groups(x: torch.Tensor, group_dims: Sequence[int], weights: Sequence[f
 
 def centroid_update(x: torch.Tensor, assignment: torch.Tensor, k: int, centers: torch.Tensor):
     """New centres = per-cluster means of x (fp64 sums) written into ``centers`` where the
-    cluster is non-empty.  Returns (centers, counts i32[k])."""
+    cluster is non-empty.  Rows whose assignment lies outside [0, k) belong to no cluster: they enter no sum and
+    no count.  Returns (centers, counts i32[k])."""
+    _require_f32("centroid_update", x, centers)
     _require_device(x, centers)
     n, d = x.shape
     b = bucket(assignment, k, rows_per_tile=centroid_tile_rows())
@@ -1429,6 +1454,7 @@ def centroid_update(x: torch.Tensor, assignment: torch.Tensor, k: int, centers: 
 
 
 def pairwise_distance(x: torch.Tensor, c: torch.Tensor) -> torch.Tensor:
+    _require_f32("pairwise_distance", x)
     c = c.float().contiguous()
     _require_device(x, c)
     n, d = x.shape
@@ -1441,6 +1467,7 @@ def pairwise_distance(x: torch.Tensor, c: torch.Tensor) -> torch.Tensor:
 def pairwise_cosine(x: torch.Tensor, c: torch.Tensor, scores: bool = False) -> torch.Tensor:
     """Cosine distances 1 - x.c / (|x||c|): fp32 [N, K], or with ``scores`` the auction's worker-major fp16
     [K][N] = -distance (include/rqsid.h rqsid_pairwise_cosine)."""
+    _require_f32("pairwise_cosine", x)
     c = c.float().contiguous()
     _require_device(x, c)
     n, d = x.shape
@@ -1457,6 +1484,7 @@ def pairwise_cosine(x: torch.Tensor, c: torch.Tensor, scores: bool = False) -> t
 
 def auction_scores(x: torch.Tensor, c: torch.Tensor, half: bool = False) -> torch.Tensor:
     """Worker-major fp16 scores W[k][n] = -distance (the auction's input), see include/rqsid.h."""
+    _require_f32("auction_scores", x)
     c = c.float().contiguous()
     _require_device(x, c)
     n, d = x.shape
@@ -1514,7 +1542,9 @@ def greedy_match(dist: torch.Tensor, sub_off: torch.Tensor, max_take: int):
 
 def centroid_sums(x: torch.Tensor, assignment: torch.Tensor, k: int):
     """Per-cluster fp64 sums and counts of the rows of x (the first half of the Lloyd update; the
-    multi-GPU fit all-reduces these).  Returns (sums f64 [k, D], counts i32 [k])."""
+    multi-GPU fit all-reduces these).  Rows whose assignment lies outside [0, k) enter no sum and no count.
+    Returns (sums f64 [k, D], counts i32 [k])."""
+    _require_f32("centroid_sums", x)
     _require_device(x)
     n, d = x.shape
     b = bucket(assignment, k, rows_per_tile=centroid_tile_rows())
@@ -1561,6 +1591,7 @@ def seg_auction_scores(x: torch.Tensor, centers: torch.Tensor, k: int, layout: S
                        half: bool = False) -> torch.Tensor:
     """Per-segment worker-major fp16 scores -distance (segment s: rows of layout, centres s*k..s*k+k-1),
     concatenated: a flat fp16 tensor of k * N values."""
+    _require_f32("seg_auction_scores", x)
     centers = centers.float().contiguous()
     _require_device(x, centers)
     n, d = x.shape

@@ -612,7 +612,12 @@ int rqsid_scale_groups(const float* x, int64_t n, int32_t dim, const int32_t* gr
 /* Lloyd centroid update, first half: per-cluster fp64 sums over the rows of
  * each segment (bucketed by rqsid_bucket with rqsid_centroid_tile_rows()).
  * sums must be zeroed by the caller.  Replaces the per-cluster
- * nonzero/index_select/mean loop of balancekmeans/__init__.py:315-324,434-443. */
+ * nonzero/index_select/mean loop of balancekmeans/__init__.py:315-324,434-443.
+ * A row whose key lies outside [0, n_segments) is in no segment of rqsid_bucket's
+ * tables, so it enters no sum and no count; the other clusters are unaffected.
+ * Every sum is an fp64 sum of the cluster's fp32 rows in an unspecified order
+ * (within count * 2^-52 * sum|x| of the exact sum), so the fp32 mean written by
+ * rqsid_centroid_finalize is the correctly rounded mean up to that sliver. */
 int32_t rqsid_centroid_tile_rows(void);
 int rqsid_centroid_accumulate(const float* x, int32_t dim, const int32_t* row_index,
                               int32_t n_segments, const int32_t* seg_row_off,
